@@ -11,14 +11,20 @@ the step ends with one RCCL all-gather of the [256, 4, 768] fp32 embeddings.
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 the driver uses
 torch.distributed.run (one rank per GPU, RANK/LOCAL_RANK/WORLD_SIZE from the env).
 
+A plain run sets up, runs W warm-up steps, times K steps and prints the JSON line; --dump-outputs DIR
+also writes the embeddings the last timed step produced ([B, 4, H], the gathered [N*B, 4, H] for N > 1)
+to DIR/embeddings.npy (float32; inputs and weights are seeded, so two builds compare output for output).
+--full adds the `roofline` and `cpu_baseline` fields, each a run of its own after the timed steps.
+
 The JSON line carries:
   value         clips/s over K steps timed without instrumentation.
-  roofline      dominant kernel (most device time): algorithmic FLOPs per launch / its mean
+  ms_per_step   wall milliseconds per timed step (elapsed / K).
+  roofline      (--full) dominant kernel (most device time): algorithmic FLOPs per launch / its mean
                 launch time, both from HIP events recorded around every launch on the launch
                 stream (sse_profile_*) during a second timed region of the same K steps
                 (profiled_ms_per_step: that region's step time, events included); traffic from
                 the committed rocprofv3 PMC summary of the same workload.
-  cpu_baseline  the reference's CPU path on this host's cores, a bounded sample of clips (rank 0,
+  cpu_baseline  (--full) the reference's CPU path on this host's cores, a bounded sample of clips (rank 0,
                 N = 1 only): WavLM = oracle/wavlm_aten.py, the reference's batch-1 loop on the same
                 ATen ops, calibrated against the reference itself ("calibrated-aten",
                 profiles/r2_cpu_baseline_calibration.json).
@@ -68,8 +74,13 @@ def parse():
                     help="fp8: Whisper only, MX-fp8 QKV / fc1 / fc2 GEMMs (BASELINE configs[4]); fp16x3: "
                          "WavLM / Whisper, split-fp16 GEMMs, fp32-class (<= 1e-4) embeddings; fp16: WavLM, the bf16 "
                          "path with fp16 activations / operands (same MFMA rate, 8 more mantissa bits)")
-    ap.add_argument("--cpu-sample", type=int, default=None, help="clips for the CPU baseline (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-launch event timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-launch event timing (roofline) and the CPU "
+                         "baseline; a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="--full: clips for the CPU baseline (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-launch event timing")
     ap.add_argument("--stream", action="store_true",
                     help="clips streamed from pinned host memory each step (double-buffered H2D on a side stream)")
     ap.add_argument("--logmel", action="store_true",
@@ -86,7 +97,29 @@ def parse():
                     help="--corpus with the clips already in HBM (default: staged from pinned host memory)")
     ap.add_argument("--ragged", action="store_true",
                     help="--corpus with mixed clip lengths (1 s .. --seconds), ragged batches")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} of the last timed step -> path/<name>.npy, float32.  Outputs that
+    together exceed 64 MB are written as a fixed seeded sample of their leading-axis rows (the same rows
+    every run), each array's share of the limit proportional to its size."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if total > DUMP_LIMIT_BYTES:
+            row = max(1, t[0].numel() * 4)
+            keep = max(1, min(t.shape[0], int(DUMP_LIMIT_BYTES * (t.numel() * 4 / total)) // row))
+            rows = np.sort(np.random.default_rng(20240229).permutation(t.shape[0])[:keep])
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32))
 
 
 def host_threads() -> int:
@@ -294,6 +327,8 @@ def logmel_run(a, dev):
                         "note": "fused STFT (LDS FFT) + |X|^2 + mel + log10 per 20-frame block, then the per-clip "
                                 "max clamp; the spectrum never leaves LDS"},
            "finite": bool(torch.isfinite(out).all().item())}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"logmel": out})
     print(json.dumps(res), flush=True)
 
 
@@ -356,6 +391,8 @@ def corpus_run(a, model, spec, idx, clips, B, L, world, rank, dev, dist):
                           "model": spec.name, "global_batch": N, "clip_samples": L, "layers_pooled": idx,
                           "parallelism": f"clip-sharded dp{world}", "staging": where},
                "finite": bool(torch.isfinite(emb).all().item()), "rows": int(emb.shape[0])}
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"embeddings": emb})
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -471,15 +508,18 @@ def main():
         return el, recs
 
     # value: an unperturbed timed region (per-launch event records add ~0.5 ms/step of launch
-    # gaps); roofline: a second timed region of the same K steps with the events (single-stream)
+    # gaps); roofline (--full): a second timed region of the same K steps with the events (single-stream)
     elapsed, _ = timed(False)
     # N > 1: the last step's gathered [world*B, 4, H] slot checked against every rank's own rows (rank-tagged
     # clips), and the world size RCCL itself reports -- outside the timed region
     gather_check = pipe.verify() if dist is not None else None
     if gather_check is not None and gather_check["rccl_world"] != world:
         raise RuntimeError(f"RCCL world {gather_check['rccl_world']} != WORLD_SIZE {world}")
+    if a.dump_outputs and rank == 0:   # the last timed step's slot: [B, 4, H], or the gathered [world*B, 4, H]
+        last = (pipe.steps - 1) % 2
+        dump_outputs(a.dump_outputs, {"embeddings": pipe.outs[last] if dist is None else pipe.gathered[last]})
     records, prof_elapsed = [], None
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         prof_elapsed, records = timed(True)
     model.check_range_now()   # fp16 / fp16x3: raises SSERangeError if any timed step overflowed
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -518,7 +558,7 @@ def main():
         if a.dtype == "fp16x3":   # the same logical FLOPs against the dense fp16 MFMA peak (3 products per term)
             res["logical_flops_frac_dense_fp16"] = round(value / world * FLOP_PER_CLIP[a.model] / 1e12 / PEAK_TFLOPS["fp16"], 4)
         ncpu = a.cpu_sample if a.cpu_sample is not None else (256 if wavlm else 2)   # ~10-30 s of CPU work
-        if world == 1 and ncpu > 0:
+        if a.full and world == 1 and ncpu > 0:
             res["cpu_baseline"] = cpu_baseline(a.model, ncpu, secs)
         print(json.dumps(res), flush=True)
     if dist is not None:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Per-kernel reduction of a rocprofv3 kernel trace of `bench.py`, with the single-stream profiled pass
-separated from the two-stream timed steps.
+"""Per-kernel reduction of a rocprofv3 kernel trace of `bench.py --full`, with the single-stream profiled
+pass separated from the two-stream timed steps.
 
-bench.py runs W + K timed steps on two streams (the half-batch split: every launch covers half the batch,
+bench.py --full runs W + K timed steps on two streams (the half-batch split: every launch covers half the batch,
 launches of the two streams overlap, so their durations are not exclusive times) and then K profiled steps
 on one stream (full-batch launches back to back, the pass its `roofline` is computed from).  In the trace the
 profiled pass is the tail of the main queue after the side queue's last launch.  This prints, for that pass,
