@@ -135,6 +135,46 @@ int sse_embed_ragged(sse_model* m, const float* d_in, const int32_t* d_lengths, 
                      const int32_t* layer_ids, int n_layers, float* d_out, void* d_ws, size_t ws_bytes,
                      void* stream);
 
+/* Statistics and windowed pooling.  The reference pools every hidden state with one time-mean,
+ * `torch.mean(hidden_state, dim=1)` (REF/WavLM_embeddings.py:321, REF/whisper_embeddings_large.py:278);
+ * sse_embed / sse_embed_ragged are that call.  sse_embed_pooled extends it without materialising the
+ * hidden states:
+ *   stats       bitmask of SSE_STAT_*; the selected statistics are written in the fixed order mean, std, max.
+ *               std is torch.std(hs, dim=1, correction=ddof), ddof 0 or 1 (a segment with count - ddof <= 0
+ *               writes 0, not NaN); max is the exact maximum of the fp32 values.
+ *   win, hop    windows of `win` frames every `hop` frames (win % hop == 0).  win = 0: one segment over the
+ *               clip's frames.  Otherwise a clip of T frames has S(T) = 1 segments if T <= win, else
+ *               1 + ceil((T - win) / hop); segment s covers frames [s hop, min(s hop + win, T)).
+ *   valid_only  Whisper: pool only the encoder frames that cover real audio, min(1500, ceil(len / 320))
+ *               of them (len = d_lengths[b], or L), instead of all 1500 frames of the 30 s pad (the
+ *               reference's behaviour and the default).  The forward itself is unchanged.  No effect on
+ *               WavLM, which pools its own frames already.
+ * d_out is [B][n_layers][S][n_stats * hidden] fp32 with S = sse_pool_segments(sse_output_frames(m, L), win,
+ * hop); sse_pool_out_floats is its size.  With d_lengths (device int32 [B], as sse_embed_ragged; NULL = full
+ * rows) a clip's segment slots at or beyond its own S(T_b), and all slots of a clip without frames, are
+ * written as zeros.  A descriptor of SSE_STAT_MEAN alone with win = 0 and valid_only = 0 makes exactly the
+ * launches of sse_embed / sse_embed_ragged.  SSE_ERR_INVALID, with nothing launched, for: stats == 0 or
+ * unknown bits, ddof outside {0, 1}, win < 0, win > 0 with hop <= 0 or win % hop != 0.
+ * Workspace: sse_workspace_bytes (for Whisper that includes the B frame counts of valid_only).  No host
+ * synchronisation: capturable into a graph like sse_embed. */
+enum { SSE_STAT_MEAN = 1, SSE_STAT_STD = 2, SSE_STAT_MAX = 4 };
+typedef struct sse_pool_desc {
+  int32_t stats, ddof, win, hop, valid_only;
+} sse_pool_desc;
+/* Segments S(T) of a clip of T frames (host-only, no device call); < 0 (SSE_ERR_INVALID) for T < 0 or a
+ * (win, hop) the rule above rejects. */
+int sse_pool_segments(int T, int win, int hop);
+/* Floats of sse_embed_pooled's d_out; 0 for invalid arguments. */
+size_t sse_pool_out_floats(const sse_model* m, int B, int L, int n_layers, const sse_pool_desc* desc);
+int sse_embed_pooled(sse_model* m, const float* d_in, const int32_t* d_lengths, int B, int L,
+                     const int32_t* layer_ids, int n_layers, const sse_pool_desc* desc, float* d_out,
+                     void* d_ws, size_t ws_bytes, void* stream);
+/* The pooling kernel on its own (test hook, no model): d_x [B][T][H] of `dtype` (SSE_DTYPE_F32 / _BF16 /
+ * _FP16), H % 4 == 0, optional d_tlen (device int32 [B] frame counts, clamped to [0, T]) ->
+ * d_out [B][S][n_stats * H] fp32, S = sse_pool_segments(T, win, hop).  valid_only is ignored. */
+int sse_pool(int dtype, const void* d_x, const int32_t* d_tlen, int B, int T, int H,
+             const sse_pool_desc* desc, float* d_out, void* stream);
+
 /* Range check of the fp16-range dtypes (SSE_DTYPE_FP16, SSE_DTYPE_FP16X3): every sse_embed /
  * sse_embed_ragged / sse_hidden_states call on such a model also scans the fp32 values it wrote and
  * raises a device flag when one is non-finite (an fp16 activation overflowed: |x| >= 65504 somewhere

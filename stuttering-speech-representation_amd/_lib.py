@@ -21,7 +21,9 @@ SSE_DTYPE_BF16 = 1
 SSE_DTYPE_FP8 = 2   # bf16 activations + MX-fp8 encoder-layer GEMMs (Whisper)
 SSE_DTYPE_FP16X3 = 3   # fp32 activations, split-fp16 (hi/lo) GEMMs: fp32-class results (WavLM-base)
 SSE_DTYPE_FP16 = 4   # the bf16 path with fp16 activations / weights / MFMA operands (WavLM-base)
+SSE_STAT_MEAN, SSE_STAT_STD, SSE_STAT_MAX = 1, 2, 4   # sse_pool_desc.stats bits (output order: mean, std, max)
 SSE_ERR_INVALID = -1
+SSE_ERR_WORKSPACE = -4
 SSE_ERR_OOM = -6
 SSE_ERR_RANGE = -7   # an fp16-range call wrote a non-finite value (sse_check_range)
 
@@ -34,7 +36,8 @@ EXPORTED = ("sse_weight_floats", "sse_model_create", "sse_model_destroy", "sse_o
             "sse_resample", "sse_augment", "sse_mx_scale_bytes", "sse_mx_scale_offset", "sse_mx_quantize",
             "sse_mx_quantize_host", "sse_gemm_mx", "sse_pitch_shift_workspace_bytes", "sse_pitch_shift",
             "sse_set_option", "sse_get_option", "sse_embed_ragged", "sse_gemm_lnfold", "sse_check_range",
-            "sse_attention", "sse_gemm_ex", "sse_attention_f8", "sse_layernorm_mx", "sse_attention_f8_mx")
+            "sse_attention", "sse_gemm_ex", "sse_attention_f8", "sse_layernorm_mx", "sse_attention_f8_mx",
+            "sse_pool_segments", "sse_pool_out_floats", "sse_embed_pooled", "sse_pool")
 
 
 class SSEError(RuntimeError):
@@ -61,6 +64,11 @@ class sse_gemm_desc(ctypes.Structure):
                                          "vamax")] + \
         [(n, ctypes.c_int32) for n in ("c_scale_rm", "vamax_rows")] + \
         [("ct2", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in ("n_split", "ldc2")]
+
+
+class sse_pool_desc(ctypes.Structure):
+    """include/sse.h sse_pool_desc (sse_embed_pooled, sse_pool)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("stats", "ddof", "win", "hop", "valid_only")]
 
 
 class sse_cfg(ctypes.Structure):
@@ -142,6 +150,15 @@ def lib() -> ctypes.CDLL:
     L.sse_embed.restype = i32
     L.sse_embed_ragged.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, sz, vp]
     L.sse_embed_ragged.restype = i32
+    if hasattr(L, "sse_embed_pooled"):   # (an earlier build loaded for an A/B has no statistics pooling)
+        L.sse_pool_segments.argtypes = [i32, i32, i32]
+        L.sse_pool_segments.restype = i32
+        L.sse_pool_out_floats.argtypes = [vp, i32, i32, i32, ctypes.POINTER(sse_pool_desc)]
+        L.sse_pool_out_floats.restype = sz
+        L.sse_embed_pooled.argtypes = [vp, vp, vp, i32, i32, vp, i32, ctypes.POINTER(sse_pool_desc), vp, vp, sz, vp]
+        L.sse_embed_pooled.restype = i32
+        L.sse_pool.argtypes = [i32, vp, vp, i32, i32, i32, ctypes.POINTER(sse_pool_desc), vp, vp]
+        L.sse_pool.restype = i32
     L.sse_check_range.argtypes = [vp, vp]
     L.sse_check_range.restype = i32
     L.sse_hidden_states.argtypes = [vp, vp, i32, i32, vp, vp, sz, vp]

@@ -247,15 +247,18 @@ def _finish_all(finish, dist, group, world: int, rank: int, start: int, stop: in
         raise ShardFinishError(f"{where}: finish() failed on rank(s) {failed}; no all-gather was issued")
 
 
-def sse_embed_fn(model, layer_indices) -> Callable[..., torch.Tensor]:
+def sse_embed_fn(model, layer_indices, *, pooling="mean", window=None, hop=None, ddof=1,
+                 valid_only=False) -> Callable[..., torch.Tensor]:
     """embed_fn for extract_corpus backed by the HIP path (SSEModel.embed): writes into ``out``,
-    ragged batches through ``lengths``."""
+    ragged batches through ``lengths``.  ``pooling`` / ``window`` / ``hop`` / ``ddof`` / ``valid_only`` are
+    SSEModel.embed's pool arguments (``out`` is then [B, n_layers, (S,) n_stats*H])."""
     idx = [int(i) for i in layer_indices]
+    pool = dict(pool=pooling, window=window, hop=hop, ddof=ddof, valid_only=valid_only)
 
     # no per-batch range check (it synchronises the stream and would cancel the staged copy / compute
     # overlap): fp16 / fp16x3 models are checked once, by finish(), after the rank's last batch
     def fn(wave, lengths=None, out=None):
-        return model.embed(wave, idx, out=out, lengths=lengths, check_range=False)
+        return model.embed(wave, idx, out=out, lengths=lengths, check_range=False, **pool)
     fn.finish = model.check_range_now
     return fn
 

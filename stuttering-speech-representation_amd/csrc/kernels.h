@@ -67,6 +67,25 @@ int launch_pool_mean(const TI* x, int B, int T, int H, float* out, long long out
                      const float2* st = nullptr, const float* w = nullptr, const float* b = nullptr,
                      const float2* part = nullptr, int nt = 0, float eps = 0.f, const int* tlen = nullptr);
 
+// Statistics / windowed pooling (sse_pool_desc without valid_only): stats = bitmask of POOL_MEAN | POOL_STD |
+// POOL_MAX, written in that order; std with correction ddof; win / hop in frames (win = 0: one segment).
+struct PoolDesc {
+  int stats, ddof, win, hop;
+};
+enum { POOL_MEAN = 1, POOL_STD = 2, POOL_MAX = 4 };
+// segments of a clip of T frames (the host twin of the kernel's rule); -1 = invalid (win, hop)
+int pool_segments(int T, int win, int hop);
+// out[b*stride_b + s*stride_s + k*H + n], k = position of the statistic among the selected ones; nseg =
+// pool_segments(T, ...) slots per clip, those past a (ragged) clip's own segments written as zeros.  The
+// LayerNorm and tlen arguments are launch_pool_mean's.
+template <typename TI>
+int launch_pool_stats(const TI* x, int B, int T, int H, float* out, long long stride_b, long long stride_s, int nseg,
+                      PoolDesc d, hipStream_t s, const float2* st = nullptr, const float* w = nullptr,
+                      const float* b = nullptr, const float2* part = nullptr, int nt = 0, float eps = 0.f,
+                      const int* tlen = nullptr);
+// Whisper valid-frame pooling: tq[b] = min(Tq, ceil(len_b / 320)), len_b = lens[b] clamped to [0, L] (lens null: L)
+int launch_whisper_frames(const int* lens, int B, int L, int Tq, int* tq, hipStream_t s);
+
 struct AttnArgs {
   const void* qkv;       // [B*T][ldq]  (q | k | v | WavLM gate projection | pad), element type T
   void* out;             // [B*T][H]

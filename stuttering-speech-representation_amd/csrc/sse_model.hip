@@ -730,6 +730,7 @@ struct WhisperWs {
   size_t vam;      // fp8 attention: per-(clip, column) max |V| (float bits), [B][D]
   size_t p1, p2;   // folded pre-LN: per-256-column (mean, M2) partials of the residual stream's rows
   size_t dx, dxb, dv, dq, dctx, dff, dxf;   // decoder rows [B][*]
+  size_t fr;       // valid-frame pooling (sse_pool_desc.valid_only): per-clip encoder frame counts [B]
 };
 
 WhisperWs whisper_plan(const sse_model* m, int B, Plan& p) {
@@ -764,6 +765,7 @@ WhisperWs whisper_plan(const sse_model* m, int B, Plan& p) {
     w.dff = p.add((size_t)B * c.dec_ffn * es);
     w.dxf = p.add((size_t)B * D * 4);
   }
+  w.fr = p.add((size_t)B * 4);
   return w;
 }
 
@@ -782,10 +784,27 @@ struct Sink {
   int B, T, H;
   hipStream_t s;
   const int* tlen = nullptr;   // ragged batch: frames of each clip (the time-means run over those)
+  // statistics / windowed pooling (sse_embed_pooled): pooled is then [B][n_ids][nseg][nst * H]
+  sse_model* m = nullptr;      // profile tags of the pool_stats launches
+  PoolDesc pd{POOL_MEAN, 1, 0, 0};
+  int valid_only = 0;          // Whisper: pool the frames that cover real audio (whisper_valid_frames)
+  int nseg = 1, nst = 1;       // segment slots per clip (pool_segments(T)), selected statistics
+  bool plain() const { return pd.stats == POOL_MEAN && pd.win == 0 && !valid_only; }
+  size_t slot() const { return (size_t)nseg * nst * H; }   // floats per (clip, layer); H on the plain path
+  template <typename TI>
+  int pool_stats(int i, const char* tag, const TI* x, const float2* st, const float* w, const float* b,
+                 const float2* part, int nt, float eps) const {
+    const double bytes = (double)B * T * H * sizeof(TI) + (double)B * slot() * 4;
+    return prof(m, s, tag, 0, bytes, [&] {
+      return launch_pool_stats<TI>(x, B, T, H, pooled + (size_t)i * slot(), (long long)n_ids * slot(),
+                                   (long long)nst * H, nseg, pd, s, st, w, b, part, nt, eps, tlen); });
+  }
   template <typename TI>
   int emit(int idx, const TI* x) const {   // fp32 or the bf16 residual stream
     for (int i = 0; i < n_ids; ++i)
-      if (ids[i] == idx)
+      if (ids[i] == idx && !plain())
+        RC(pool_stats<TI>(i, "pool_stats:hs", x, nullptr, nullptr, nullptr, nullptr, 0, 0.f));
+      else if (ids[i] == idx)
         RC(launch_pool_mean<TI>(x, B, T, H, pooled + (size_t)i * H, (long long)n_ids * H, s, nullptr, nullptr, nullptr,
                                 nullptr, 0, 0.f, tlen));
     if (hs) {
@@ -805,7 +824,9 @@ struct Sink {
   int emit_ln(int idx, const TI* x, const float2* st, const float* w, const float* b, float eps,
               const float2* part = nullptr, int nt = 0) const {
     for (int i = 0; i < n_ids; ++i)
-      if (ids[i] == idx)
+      if (ids[i] == idx && !plain())
+        RC(pool_stats<TI>(i, "pool_stats:hs_ln", x, st, w, b, part, nt, eps));
+      else if (ids[i] == idx)
         RC(launch_pool_mean<TI>(x, B, T, H, pooled + (size_t)i * H, (long long)n_ids * H, s, st, w, b, part, nt, eps,
                                 tlen));
     if (hs)
@@ -1331,12 +1352,23 @@ int whisper_decoder(sse_model* m, const T* enc, int B, const Sink& sink, char* w
   return sink.emit(c.decoder_layers, xf);
 }
 
+// Valid-frame pooling (sse_pool_desc.valid_only): the encoder sink pools each clip's first
+// min(Tq, ceil(len / 320)) frames, counted on the device into the workspace; the forward is unchanged.
+int whisper_valid_frames(const sse_model* m, Sink& sink, const int* lens, int B, int L, int* tq, hipStream_t s) {
+  if (!sink.valid_only || !sink.pooled) return 0;
+  RC(launch_whisper_frames(lens, B, L, m->cfg.max_positions, tq, s));
+  sink.tlen = tq;
+  return 0;
+}
+
 template <typename T>
-int whisper_forward(sse_model* m, const float* wave, int B, int L, const Sink& sink, char* ws, hipStream_t s,
+int whisper_forward(sse_model* m, const float* wave, int B, int L, const Sink& sink_in, char* ws, hipStream_t s,
                     const float* mel_hf = nullptr, const Sink* dsink = nullptr, const int* lens = nullptr) {
   const sse_cfg& c = m->cfg;
   Plan p;
   const WhisperWs w = whisper_plan(m, B, p);
+  Sink sink = sink_in;
+  RC(whisper_valid_frames(m, sink, lens, B, L, (int*)(ws + w.fr), s));
   const int D = c.hidden, F = c.ffn, nh = c.heads, Tq = c.max_positions, T2 = 2 * Tq, nm = c.n_mels;
   const int M = B * Tq;
   const float eps = c.ln_eps;
@@ -1520,11 +1552,13 @@ int whisper_forward(sse_model* m, const float* wave, int B, int L, const Sink& s
 // (fp32 softmax, f16 matrix-core products of split operands) writes the out-projection's tripled operand,
 // fc1's epilogue the fc2 operand with erf-GELU; log-mel, conv1 / conv2 (exact-f32 MFMA, 0.7 % of the FLOPs),
 // the residual stream and the 1-token decoder stay fp32.
-int whisper_forward_x3(sse_model* m, const float* wave, int B, int L, const Sink& sink, char* ws, hipStream_t s,
+int whisper_forward_x3(sse_model* m, const float* wave, int B, int L, const Sink& sink_in, char* ws, hipStream_t s,
                        const float* mel_hf, const Sink* dsink, const int* lens) {
   const sse_cfg& c = m->cfg;
   Plan p;
   const WhisperWs w = whisper_plan(m, B, p);
+  Sink sink = sink_in;
+  RC(whisper_valid_frames(m, sink, lens, B, L, (int*)(ws + w.fr), s));
   const int D = c.hidden, F = c.ffn, nh = c.heads, Tq = c.max_positions, T2 = 2 * Tq, nm = c.n_mels;
   const int M = B * Tq;
   const float eps = c.ln_eps;
@@ -1687,7 +1721,7 @@ int split_forward(sse_model* m, const float* d_in, int B, int L, const Sink& sin
     if ((i || mk) && hipStreamWaitEvent(si, m->ev_fork, 0) != hipSuccess) return SSE_ERR_HIP;
     Sink sk = sink;
     sk.B = Bi;
-    sk.pooled = sink.pooled + (size_t)b0 * sink.n_ids * sink.H;
+    sk.pooled = sink.pooled + (size_t)b0 * sink.n_ids * sink.slot();
     sk.s = si;
     const int r = forward_one(m, d_in + (size_t)b0 * L, Bi, L, sk, ws + off, si, false, nullptr, lens ? lens + b0 : nullptr);
     rc = rc ? rc : r;
@@ -1724,7 +1758,7 @@ int forward(sse_model* m, const float* d_in, int B, int L, const Sink& sink, voi
   const int rc = forward_any(m, d_in, B, L, sink, d_ws, ws_bytes, s, from_mel, dsink, lens);
   if (rc || !(m->h16() || m->x3())) return rc;
   int* flag = (int*)(m->dmem + m->status);
-  if (sink.pooled) RC(launch_finite_flag(sink.pooled, (long long)B * sink.n_ids * sink.H, flag, s));
+  if (sink.pooled) RC(launch_finite_flag(sink.pooled, (long long)B * sink.n_ids * (long long)sink.slot(), flag, s));
   if (sink.hs) RC(launch_finite_flag(sink.hs, (long long)(m->cfg.layers + 1) * B * sink.T * sink.H, flag, s));
   return 0;
 }
@@ -1972,6 +2006,57 @@ int sse_embed_ragged(sse_model* m, const float* d_in, const int32_t* d_lengths, 
     if (layer_ids[i] < 0 || layer_ids[i] > m->cfg.layers) return SSE_ERR_INVALID;
   Sink sk{layer_ids, n_layers, d_out, nullptr, B, hs_frames(m, L), m->cfg.hidden, (hipStream_t)stream};
   return forward(m, d_in, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream, false, nullptr, (const int*)d_lengths);
+}
+
+int sse_pool_segments(int T, int win, int hop) {
+  const int S = pool_segments(T, win, hop);
+  return S < 0 ? SSE_ERR_INVALID : S;
+}
+
+static bool pool_desc_ok(const sse_pool_desc* d) {
+  return d && d->stats != 0 && !(d->stats & ~(SSE_STAT_MEAN | SSE_STAT_STD | SSE_STAT_MAX)) && (d->ddof == 0 || d->ddof == 1) &&
+         d->win >= 0 && (d->win == 0 || (d->hop > 0 && d->win % d->hop == 0));
+}
+static int pool_nstats(const sse_pool_desc* d) { return (d->stats & 1) + ((d->stats >> 1) & 1) + ((d->stats >> 2) & 1); }
+
+size_t sse_pool_out_floats(const sse_model* m, int B, int L, int n_layers, const sse_pool_desc* d) {
+  if (!m || B <= 0 || L <= 0 || n_layers <= 0 || !pool_desc_ok(d)) return 0;
+  const int T = hs_frames(m, L);
+  if (T <= 0) return 0;
+  return (size_t)B * n_layers * pool_segments(T, d->win, d->hop) * pool_nstats(d) * m->cfg.hidden;
+}
+
+int sse_embed_pooled(sse_model* m, const float* d_in, const int32_t* d_lengths, int B, int L, const int32_t* layer_ids,
+                     int n_layers, const sse_pool_desc* d, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!m || !layer_ids || n_layers <= 0 || !d_out || !pool_desc_ok(d)) return SSE_ERR_INVALID;
+  for (int i = 0; i < n_layers; ++i)
+    if (layer_ids[i] < 0 || layer_ids[i] > m->cfg.layers) return SSE_ERR_INVALID;
+  if (B <= 0 || L <= 0) return SSE_ERR_INVALID;
+  const int T = hs_frames(m, L);
+  if (T <= 0) return SSE_ERR_INVALID;
+  Sink sk{layer_ids, n_layers, d_out, nullptr, B, T, m->cfg.hidden, (hipStream_t)stream};
+  sk.m = m;
+  sk.pd = PoolDesc{d->stats, d->ddof, d->win, d->hop};
+  sk.valid_only = d->valid_only != 0 && m->cfg.kind == SSE_KIND_WHISPER;
+  sk.nseg = pool_segments(T, d->win, d->hop);
+  sk.nst = pool_nstats(d);
+  // (a plain-mean description without valid-frame pooling takes the unchanged pool_mean launches: Sink::plain)
+  return forward(m, d_in, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream, false, nullptr, (const int*)d_lengths);
+}
+
+int sse_pool(int dtype, const void* d_x, const int32_t* d_tlen, int B, int T, int H, const sse_pool_desc* d,
+             float* d_out, void* stream) {
+  if (!d_x || !d_out || B <= 0 || T <= 0 || H <= 0 || H % 4 || !pool_desc_ok(d)) return SSE_ERR_INVALID;
+  const PoolDesc pd{d->stats, d->ddof, d->win, d->hop};
+  const int S = pool_segments(T, d->win, d->hop), nst = pool_nstats(d);
+  const long long ss = (long long)nst * H, sb = ss * S;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if (dtype == SSE_DTYPE_F32) rc = launch_pool_stats<float>((const float*)d_x, B, T, H, d_out, sb, ss, S, pd, s, nullptr, nullptr, nullptr, nullptr, 0, 0.f, (const int*)d_tlen);
+  else if (dtype == SSE_DTYPE_BF16) rc = launch_pool_stats<bf16>((const bf16*)d_x, B, T, H, d_out, sb, ss, S, pd, s, nullptr, nullptr, nullptr, nullptr, 0, 0.f, (const int*)d_tlen);
+  else if (dtype == SSE_DTYPE_FP16) rc = launch_pool_stats<f16>((const f16*)d_x, B, T, H, d_out, sb, ss, S, pd, s, nullptr, nullptr, nullptr, nullptr, 0, 0.f, (const int*)d_tlen);
+  else return SSE_ERR_INVALID;
+  return rc == -2 ? SSE_ERR_HIP : (rc ? SSE_ERR_INVALID : SSE_OK);
 }
 
 int sse_hidden_states(sse_model* m, const float* d_in, int B, int L, float* d_hs, void* d_ws, size_t ws_bytes,

@@ -24,6 +24,7 @@ import torch
 
 from ._lib import SSEOutOfMemoryError
 from .hf import WavLMModel, WhisperModel
+from .model import POOL_STATS, pool_mask
 
 logger = logging.getLogger(__name__)
 
@@ -94,18 +95,44 @@ def _is_oom(e: BaseException) -> bool:
     return isinstance(e, (torch.OutOfMemoryError, SSEOutOfMemoryError))
 
 
-def _pool_generic(hidden_states, layer_indices, prefix):
+def _pool_torch(h, pooling, ddof=1):
+    """[B, T, H] -> [B, n_stats*H]: the statistics of SSEModel.embed(pool=pooling) with torch (mean, std, max
+    order; std of a single frame with ddof=1 is 0, as the kernel writes it)."""
+    mask = pool_mask(pooling)
+    parts = []
+    if mask & POOL_STATS["mean"]:
+        parts.append(torch.mean(h, dim=1))
+    if mask & POOL_STATS["std"]:
+        parts.append(torch.std(h, dim=1, correction=ddof) if h.shape[1] - ddof > 0 else torch.zeros_like(h[:, 0]))
+    if mask & POOL_STATS["max"]:
+        parts.append(torch.amax(h, dim=1))
+    return torch.cat(parts, dim=-1)
+
+
+def _no_window(window):
+    if window is not None:
+        raise ValueError("window= gives several vectors per layer; the dict-returning extract functions keep one: "
+                         "use SSEModel.embed(window=, hop=)")
+
+
+def _pool_generic(hidden_states, layer_indices, prefix, pooling="mean"):
     out = {}
     for idx in layer_indices:
-        if idx < len(hidden_states):
+        if idx < len(hidden_states) and pooling != "mean":
+            out[f"{prefix}{idx}"] = _pool_torch(hidden_states[idx], pooling).cpu().numpy().flatten()
+        elif idx < len(hidden_states):
             out[f"{prefix}{idx}"] = torch.mean(hidden_states[idx], dim=1).cpu().numpy().flatten()
         else:
             logger.warning(f"Layer {idx} is out of range (max: {len(hidden_states) - 1})")
     return out
 
 
-def extract_embeddings_from_audio_wavlm(audio_array, model, feature_extractor, device, layer_indices):
-    """REF/model_training_1.py:235-266 (in-memory twin)."""
+def extract_embeddings_from_audio_wavlm(audio_array, model, feature_extractor, device, layer_indices, *,
+                                        pooling="mean", window=None):
+    """REF/model_training_1.py:235-266 (in-memory twin).  ``pooling`` (keyword-only, default the reference's
+    time-mean): "std" | "max" | "mean_std" | "mean_std_max" | a tuple of names -> float32[n_stats*H] per key."""
+    _no_window(window)
+    pool_mask(pooling)
     try:
         inputs = feature_extractor(audio_array, sampling_rate=16000, return_tensors="pt").to(device)
         with torch.no_grad():
@@ -117,10 +144,10 @@ def extract_embeddings_from_audio_wavlm(audio_array, model, feature_extractor, d
                         logger.warning(f"Layer {i} is out of range (max: {n_hs - 1})")
                 if not valid:
                     return {}
-                emb = model.embed(inputs.input_values, valid).cpu().numpy()
+                emb = model.embed(inputs.input_values, valid, pooling=pooling).cpu().numpy()
                 return {f"layer_{i}": emb[0, j].copy() for j, i in enumerate(valid)}
             outputs = model(inputs.input_values, output_hidden_states=True, return_dict=True)
-            return _pool_generic(outputs.hidden_states, layer_indices, "layer_")
+            return _pool_generic(outputs.hidden_states, layer_indices, "layer_", pooling)
     except Exception as e:
         if _is_oom(e):
             logger.error("HIP out of memory while extracting WavLM embeddings")
@@ -131,24 +158,31 @@ def extract_embeddings_from_audio_wavlm(audio_array, model, feature_extractor, d
 
 
 def extract_wavlm_embeddings(audio_file, model, feature_extractor, device, layer_indices, max_length=None,
-                             sample_rate=16000):
-    """REF/WavLM_embeddings.py:267-341."""
+                             sample_rate=16000, *, pooling="mean", window=None):
+    """REF/WavLM_embeddings.py:267-341.  ``pooling``: as extract_embeddings_from_audio_wavlm."""
+    _no_window(window)
+    pool_mask(pooling)
     audio = load_audio(audio_file, target_sr=sample_rate, max_length=max_length, device=device)
     if audio is None:
         return None
     if audio.shape[-1] > 500000:
         logger.warning(f"Very long input ({audio.shape[-1]} samples, ~{audio.shape[-1] / sample_rate:.2f}s). "
                        "This may cause memory issues.")
-    out = extract_embeddings_from_audio_wavlm(audio, model, feature_extractor, device, layer_indices)
+    out = extract_embeddings_from_audio_wavlm(audio, model, feature_extractor, device, layer_indices, pooling=pooling)
     if out is None:
         logger.error(f"Error extracting embeddings for {audio_file}")
     return out
 
 
-def extract_embeddings_from_audio_whisper(audio_array, model, processor, device, layer_names):
+def extract_embeddings_from_audio_whisper(audio_array, model, processor, device, layer_names, *, pooling="mean",
+                                          window=None, valid_only=False):
     """REF/model_training_1.py:268-316 (in-memory twin): ``encoder_layer_<i>`` time-means and
     ``decoder_layer_<i>`` states of the 1-token decoder pass, in ``layer_names`` order.  A model
-    built without the decoder (decoder_layers=0) reports and skips decoder names."""
+    built without the decoder (decoder_layers=0) reports and skips decoder names.  ``pooling`` (keyword-only)
+    selects the statistics of the encoder vectors (float32[n_stats*H]; the 1-token decoder states stay [H]);
+    ``valid_only`` pools the encoder frames that cover the clip instead of the 30 s pad."""
+    _no_window(window)
+    pool_mask(pooling)
     try:
         wanted = []
         for n in layer_names:
@@ -165,7 +199,7 @@ def extract_embeddings_from_audio_whisper(audio_array, model, processor, device,
                 if not enc and not dec:
                     return {}
                 wave = torch.from_numpy(np.ascontiguousarray(np.asarray(audio_array, np.float32)))
-                e, dd = model.sse.whisper_embed(wave.to(model.sse.device), enc, dec)
+                e, dd = model.sse.whisper_embed(wave.to(model.sse.device), enc, dec, pool=pooling, valid_only=valid_only)
                 e, dd = e.cpu().numpy(), dd.cpu().numpy()
                 out = {}
                 for d, i, n in wanted:
@@ -186,6 +220,11 @@ def extract_embeddings_from_audio_whisper(audio_array, model, processor, device,
                 states = do.hidden_states if d else eo.hidden_states
                 if i < len(states):
                     h = states[i]
+                    if not d and valid_only:
+                        h = h[:, :min(h.shape[1], -(-int(np.asarray(audio_array).shape[-1]) // 320))]
+                    if not d and pooling != "mean":
+                        out[n] = _pool_torch(h, pooling).cpu().numpy().flatten()
+                        continue
                     out[n] = (h.squeeze(1) if d else torch.mean(h, dim=1)).cpu().numpy().flatten()
             return out
     except Exception as e:
@@ -197,8 +236,12 @@ def extract_embeddings_from_audio_whisper(audio_array, model, processor, device,
         return None
 
 
-def extract_whisper_embeddings_fixed(audio_file, model, processor, device, encoder_indices, decoder_indices):
-    """REF/whisper_embeddings_large.py:234-299: encoder time-means + 1-token decoder states."""
+def extract_whisper_embeddings_fixed(audio_file, model, processor, device, encoder_indices, decoder_indices, *,
+                                     pooling="mean", window=None, valid_only=False):
+    """REF/whisper_embeddings_large.py:234-299: encoder time-means + 1-token decoder states.
+    ``pooling`` / ``valid_only``: as extract_embeddings_from_audio_whisper."""
+    _no_window(window)
+    pool_mask(pooling)
     audio = load_audio(audio_file, device=device)
     if audio is None:
         return None
@@ -210,4 +253,5 @@ def extract_whisper_embeddings_fixed(audio_file, model, processor, device, encod
             if model.sse.spec.decoder_layers and i >= model.sse.spec.decoder_layers + 1:
                 logger.warning(f"Decoder layer {i} is out of range (max: {model.sse.spec.decoder_layers})")
     names = [f"encoder_layer_{i}" for i in encoder_indices] + [f"decoder_layer_{i}" for i in decoder_indices]
-    return extract_embeddings_from_audio_whisper(audio, model, processor, device, names)
+    return extract_embeddings_from_audio_whisper(audio, model, processor, device, names, pooling=pooling,
+                                                 valid_only=valid_only)

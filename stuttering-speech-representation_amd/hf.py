@@ -173,8 +173,11 @@ class _DuckModel:
     def eval(self):
         return self
 
-    def embed(self, wave, layer_indices):
-        return self.sse.embed(wave, layer_indices)
+    def embed(self, wave, layer_indices, *, pooling="mean", window=None, hop=None, ddof=1, valid_only=False):
+        """SSEModel.embed; ``pooling`` and the other keyword-only arguments are its pool / window / hop / ddof /
+        valid_only (the defaults are the reference's time-mean)."""
+        return self.sse.embed(wave, layer_indices, pool=pooling, window=window, hop=hop, ddof=ddof,
+                              valid_only=valid_only)
 
 
 class WavLMModel(_DuckModel):

@@ -26,6 +26,43 @@ DTYPES = {"fp32": _lib.SSE_DTYPE_F32, "float32": _lib.SSE_DTYPE_F32, "f32": _lib
 FP16_RANGE = ("fp16", "float16", "fp16x3")
 
 
+# statistics pooling: names of SSEModel.embed(pool=) -> sse_pool_desc.stats bits (output order mean, std, max)
+POOL_STATS = {"mean": _lib.SSE_STAT_MEAN, "std": _lib.SSE_STAT_STD, "max": _lib.SSE_STAT_MAX}
+
+
+def pool_mask(pool) -> int:
+    """"mean" | "std" | "max" | "mean_std" | "mean_std_max" | a tuple of names -> the statistics bitmask."""
+    names = pool.split("_") if isinstance(pool, str) else list(pool) if isinstance(pool, (tuple, list)) else None
+    if not names or any(n not in POOL_STATS for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"pool must be one of mean, std, max, mean_std, mean_std_max or a tuple of those names, "
+                         f"got {pool!r}")
+    if isinstance(pool, str) and pool not in ("mean", "std", "max", "mean_std", "mean_std_max"):
+        raise ValueError(f"unknown pool {pool!r} (pass a tuple of names for other combinations)")
+    mask = 0
+    for n in names:
+        mask |= POOL_STATS[n]
+    return mask
+
+
+def pool_desc(pool="mean", window=None, hop=None, ddof=1, valid_only=False) -> _lib.sse_pool_desc:
+    """Validate the pooling arguments (host only) and build the sse_pool_desc."""
+    mask = pool_mask(pool)
+    if ddof not in (0, 1):
+        raise ValueError(f"ddof must be 0 or 1, got {ddof!r}")
+    if (window is None) != (hop is None):
+        raise ValueError("window and hop go together (both in frames)")
+    win = 0
+    if window is not None:
+        win, hop = int(window), int(hop)
+        if win <= 0 or hop <= 0 or win % hop:
+            raise ValueError(f"window must be a positive multiple of hop, got window={window!r}, hop={hop!r}")
+    return _lib.sse_pool_desc(mask, int(ddof), win, int(hop or 0), int(bool(valid_only)))
+
+
+def _n_stats(desc) -> int:
+    return bin(desc.stats).count("1")
+
+
 def _as_numpy(v) -> np.ndarray:
     if isinstance(v, torch.Tensor):
         v = v.detach().to("cpu", torch.float32).numpy()
@@ -172,12 +209,34 @@ class SSEModel:
         _lib.check(_lib.lib().sse_profile_stop(self._h), "sse_profile_stop")
 
     # -- compute --------------------------------------------------------------------------
+    def pool_segments(self, n_samples: int, window=None, hop=None, valid_only: bool = False) -> int:
+        """Segments embed(window=, hop=) fills for a clip of n_samples (the rest of its slots are zeros)."""
+        d = pool_desc("mean", window, hop, 1, valid_only)
+        T = self.output_frames(n_samples)
+        if d.valid_only and isinstance(self.spec, WhisperSpec):
+            T = min(T, -(-int(n_samples) // 320))
+        if T <= 0:
+            return 0
+        return int(_lib.lib().sse_pool_segments(int(T), d.win, d.hop))
+
     def embed(self, wave: torch.Tensor, layer_indices, out: torch.Tensor | None = None,
-              lengths=None, workspace: torch.Tensor | None = None, check_range: bool | None = None) -> torch.Tensor:
+              lengths=None, workspace: torch.Tensor | None = None, check_range: bool | None = None, *,
+              pool="mean", window=None, hop=None, ddof: int = 1, valid_only: bool = False) -> torch.Tensor:
         """[B, L] fp32 16 kHz waves -> [B, len(layer_indices), H] fp32 time-means of hidden states.
         ``lengths`` (ragged batch): samples of each clip, its first lengths[b] samples of row b; each
         clip is embedded at its own length (sse_embed_ragged).  ``check_range`` overrides the model's
-        per-call fp16-range check (False in throughput loops, which call check_range_now() once)."""
+        per-call fp16-range check (False in throughput loops, which call check_range_now() once).
+
+        Statistics pooling (sse_embed_pooled): ``pool`` = "mean" | "std" | "max" | "mean_std" |
+        "mean_std_max" | a tuple of names selects the statistics, concatenated in the order mean, std, max
+        -> [B, n_layers, n_stats*H]; std is ``torch.std(hs, dim=1, correction=ddof)``.  ``window`` / ``hop``
+        (frames, window % hop == 0) pool windows instead of the clip -> [B, n_layers, S, n_stats*H];
+        a shorter clip of a ragged batch fills its first ``pool_segments(n_samples, window, hop)`` slots, the
+        rest are zeros.  ``valid_only`` (Whisper): pool the ceil(n_samples / 320) frames that cover the clip,
+        not the 30 s pad.  With all of these at their defaults the call is the plain time-mean above."""
+        desc = pool_desc(pool, window, hop, ddof, valid_only)
+        if not (desc.stats == _lib.SSE_STAT_MEAN and desc.win == 0 and not desc.valid_only):
+            return self._embed_pooled(wave, layer_indices, out, lengths, workspace, check_range, desc)
         wave = self._check_wave(wave)
         B, L = wave.shape
         ids = torch.tensor([int(i) for i in layer_indices], dtype=torch.int32)
@@ -210,15 +269,50 @@ class SSEModel:
         self._after(check_range)
         return out
 
-    def embed_clips(self, clips, layer_indices) -> torch.Tensor:
+    def _embed_pooled(self, wave, layer_indices, out, lengths, workspace, check_range, desc) -> torch.Tensor:
+        wave = self._check_wave(wave)
+        B, L = wave.shape
+        ids = torch.tensor([int(i) for i in layer_indices], dtype=torch.int32)
+        n = ids.numel()
+        T = self.output_frames(L)
+        if T <= 0:
+            raise _lib.SSEError(-1, "a clip is shorter than the conv receptive field")
+        S = int(_lib.lib().sse_pool_segments(T, desc.win, desc.hop))
+        width = _n_stats(desc) * self.spec.hidden
+        shape = (B, n, S, width) if desc.win else (B, n, width)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif (out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != shape
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous fp32 {list(shape)} tensor on {self.device}")
+        assert out.numel() == _lib.lib().sse_pool_out_floats(self._h, B, L, n, ctypes.byref(desc))
+        ws = self.workspace(B, L) if workspace is None else workspace
+        if ws.numel() < _lib.lib().sse_workspace_bytes(self._h, int(B), int(L)):
+            raise ValueError("workspace too small")
+        d_len = None
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            if len(lens) != B or min(lens) < 1 or max(lens) > L:
+                raise ValueError(f"lengths must be {B} values in [1, {L}]")
+            if isinstance(self.spec, WavLMSpec) and min(self.spec.frames(v) for v in lens) <= 0:
+                raise _lib.SSEError(-1, "a clip is shorter than the conv receptive field")
+            d_len = torch.tensor(lens, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+        _lib.check(_lib.lib().sse_embed_pooled(self._h, wave.data_ptr(), d_len.data_ptr() if d_len is not None else None,
+                                               B, L, ids.data_ptr(), n, ctypes.byref(desc), out.data_ptr(),
+                                               ws.data_ptr(), ws.numel(), self._stream()), "sse_embed_pooled")
+        self._after(check_range)
+        return out
+
+    def embed_clips(self, clips, layer_indices, **pooling) -> torch.Tensor:
         """A list of 1-D clips of any lengths -> [N, len(layer_indices), H]: one ragged batch
-        (zero-padded rows + lengths), every clip embedded at its own length."""
+        (zero-padded rows + lengths), every clip embedded at its own length.  ``pooling``: the
+        pool / window / hop / ddof / valid_only arguments of ``embed``."""
         lens = [int(c.shape[-1]) for c in clips]
         wave = torch.zeros((len(clips), max(lens)), dtype=torch.float32, device=self.device)
         for i, c in enumerate(clips):
             c = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.asarray(c, dtype=np.float32))
             wave[i, :lens[i]] = c.to(self.device, torch.float32)
-        return self.embed(wave, layer_indices, lengths=lens)
+        return self.embed(wave, layer_indices, lengths=lens, **pooling)
 
     def hidden_states(self, wave: torch.Tensor) -> tuple:
         """[B, L] -> tuple of layers+1 tensors [B, T, H] (HF ``output_hidden_states`` semantics)."""
@@ -253,13 +347,25 @@ class SSEModel:
         return tuple(hs.unbind(0))
 
 
-    def whisper_embed(self, wave: torch.Tensor, encoder_indices, decoder_indices, enc_out=None, dec_out=None):
+    def whisper_embed(self, wave: torch.Tensor, encoder_indices, decoder_indices, enc_out=None, dec_out=None, *,
+                      pool="mean", window=None, hop=None, ddof: int = 1, valid_only: bool = False):
         """Whisper: encoder time-means AND 1-token decoder states in one pass
-        (REF/whisper_embeddings_large.py:234-299) -> ([B, n_enc, H], [B, n_dec, H]) fp32."""
+        (REF/whisper_embeddings_large.py:234-299) -> ([B, n_enc, H], [B, n_dec, H]) fp32.
+        The pooling arguments (``embed``) apply to the encoder output only (the decoder has one token);
+        a non-default pooling runs the encoder statistics and the decoder states as two calls."""
         if not isinstance(self.spec, WhisperSpec):
             raise TypeError("whisper_embed is Whisper-only")
         if decoder_indices and not self.spec.decoder_layers:
             raise ValueError(f"{self.spec.name} was built without the decoder (decoder_layers=0)")
+        desc = pool_desc(pool, window, hop, ddof, valid_only)
+        if not (desc.stats == _lib.SSE_STAT_MEAN and desc.win == 0 and not desc.valid_only):
+            if len(encoder_indices):
+                enc_out = self._embed_pooled(wave, encoder_indices, enc_out, None, None, None, desc)
+            else:
+                enc_out = torch.empty((self._check_wave(wave).shape[0], 0, _n_stats(desc) * self.spec.hidden),
+                                      dtype=torch.float32, device=self.device)
+            _, dec_out = self.whisper_embed(wave, [], decoder_indices, None, dec_out)
+            return enc_out, dec_out
         wave = self._check_wave(wave)
         B, L = wave.shape
         H = self.spec.hidden
@@ -306,6 +412,30 @@ def logmel(wave: torch.Tensor, n_mels: int = 80) -> torch.Tensor:
     out = torch.empty((B, n_mels, 3000), dtype=torch.float32, device=wave.device)
     _lib.check(L_.sse_logmel(wave.data_ptr(), B, L, n_mels, out.data_ptr(), ws.data_ptr(), n,
                              ctypes.c_void_p(torch.cuda.current_stream(wave.device).cuda_stream)), "sse_logmel")
+    return out
+
+
+def pool_states(x: torch.Tensor, lengths=None, pool="mean", window=None, hop=None, ddof: int = 1) -> torch.Tensor:
+    """The statistics-pooling kernel on its own (sse_pool): x [B, T, H] fp32 / bf16 / fp16 on the GPU, H % 4 == 0,
+    optional per-clip frame counts ``lengths`` -> [B, n_stats*H], or [B, S, n_stats*H] with ``window`` / ``hop``
+    (the arguments of ``SSEModel.embed``)."""
+    desc = pool_desc(pool, window, hop, ddof)
+    dts = {torch.float32: _lib.SSE_DTYPE_F32, torch.bfloat16: _lib.SSE_DTYPE_BF16, torch.float16: _lib.SSE_DTYPE_FP16}
+    if x.dim() != 3 or x.dtype not in dts or not x.is_cuda:
+        raise TypeError("x must be a [B, T, H] fp32 / bf16 / fp16 tensor on the GPU")
+    x = x.contiguous()
+    B, T, H = x.shape
+    S = int(_lib.lib().sse_pool_segments(T, desc.win, desc.hop))
+    width = _n_stats(desc) * H
+    out = torch.empty((B, S, width) if desc.win else (B, width), dtype=torch.float32, device=x.device)
+    d_len = None
+    if lengths is not None:
+        d_len = torch.as_tensor(lengths, dtype=torch.int32).to(x.device)
+        if d_len.numel() != B:
+            raise ValueError(f"lengths must hold {B} frame counts")
+    _lib.check(_lib.lib().sse_pool(dts[x.dtype], x.data_ptr(), d_len.data_ptr() if d_len is not None else None, B, T, H,
+                                   ctypes.byref(desc), out.data_ptr(),
+                                   ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "sse_pool")
     return out
 
 
