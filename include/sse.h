@@ -205,6 +205,60 @@ int sse_whisper_embed(sse_model* m, const float* d_wave, int B, int L, const int
 int sse_whisper_decoder_hidden_states(sse_model* m, const float* d_enc, int B, float* d_hs, void* d_ws,
                                       size_t ws_bytes, void* stream);
 
+/* ---- Whisper audio context (no reference counterpart; whisper.cpp exposes the same thing as audio_ctx) ----
+ * A Whisper call without a context encodes cfg.max_positions = 1500 frames, the 30 s pad of the feature
+ * extractor, whatever the clip's length.  The *_ctx twins below take the encoder frames F of the call,
+ * 1 <= F <= cfg.max_positions, and compute only those.  One definition for every dtype and entry point:
+ *   - each clip is cut to its first min(len, 320 F) samples (len = d_lengths[b], or L) and zero-padded;
+ *   - its log-mel is the usual Whisper log-mel restricted to the mel frames [0, 2F), the per-clip maximum of the
+ *     -8 clamp taken over those frames only;
+ *   - the encoder is HF's encoder on input_features[:, :, :2F] with embed_positions.weight[:F]: conv1 / conv2
+ *     zero-pad at mel frame 2F, attention runs over F keys (a shorter clip of the batch sees zero padding up to
+ *     F, unmasked, as it sees padding up to 1500 without a context), the final LayerNorm is unchanged;
+ *   - hidden states are [B][F][hidden]; pooling, sse_pool_segments and valid_only (min(F, ceil(len / 320))
+ *     frames) run over F frames; the one-token decoder cross-attends over the F encoder frames.
+ * F is a per-call argument (the library keeps no state); all clips of a call share it.  F = cfg.max_positions
+ * makes exactly the launches of the call without a context (bit-identical results).  Embeddings at different F
+ * are different features, not a precision mode.  The SSE_DTYPE_FP8 path runs the bf16 attention
+ * kernel instead of the fp8 one when F < 64.
+ * Every *_ctx call returns SSE_ERR_INVALID (size functions: 0), with nothing launched, for F out of range or a
+ * WavLM handle; the other arguments, results and errors are those of the call it twins. */
+/* min(cfg.max_positions, max(1, ceil(n_samples / 320))): the smallest context that covers n_samples of audio.
+ * Host-only.  SSE_ERR_INVALID for a WavLM handle. */
+int sse_whisper_context_frames(const sse_model* m, int n_samples);
+/* sse_output_frames with a context: F itself. */
+int sse_output_frames_ctx(const sse_model* m, int L, int frames);
+/* sse_workspace_bytes with a context: every B * T term of the plan scales with F (non-decreasing in F, equal to
+ * sse_workspace_bytes at F = cfg.max_positions), which is what lets a caller raise B.  (SSE_DTYPE_FP8 with fewer
+ * than 8 rows B * F: the MX operand regions are sized by their 256-row scale tiles, not by B * F.) */
+size_t sse_workspace_bytes_ctx(const sse_model* m, int B, int L, int frames);
+/* sse_logmel with a context (no handle: 1 <= F <= 1500): d_wave [B][L] -> d_mel [B][n_mels][2F] fp32, the log-mel
+ * of each clip cut at 320 F samples, frames [0, 2F).  Needs sse_logmel_workspace_bytes_ctx(B, n_mels, F). */
+size_t sse_logmel_workspace_bytes_ctx(int B, int n_mels, int frames);
+int sse_logmel_ctx(const float* d_wave, int B, int L, int n_mels, int frames, float* d_mel, void* d_ws,
+                   size_t ws_bytes, void* stream);
+/* sse_embed_pooled with a context.  d_lengths and desc are both nullable: desc == NULL is the plain time-mean, so
+ * the call also covers sse_embed (d_lengths == NULL) and sse_embed_ragged.  d_out as sse_embed_pooled with
+ * S = sse_pool_segments(F, win, hop); sse_pool_out_floats_ctx is its size (desc required there). */
+size_t sse_pool_out_floats_ctx(const sse_model* m, int B, int L, int frames, int n_layers, const sse_pool_desc* desc);
+int sse_embed_pooled_ctx(sse_model* m, const float* d_in, const int32_t* d_lengths, int B, int L, int frames,
+                         const int32_t* layer_ids, int n_layers, const sse_pool_desc* desc, float* d_out,
+                         void* d_ws, size_t ws_bytes, void* stream);
+/* sse_hidden_states with a context: d_hs [layers+1][B][F][hidden] fp32. */
+int sse_hidden_states_ctx(sse_model* m, const float* d_in, int B, int L, int frames, float* d_hs, void* d_ws,
+                          size_t ws_bytes, void* stream);
+/* sse_whisper_hidden_states_from_mel with a context: d_mel [B][n_mels][2F] fp32 (sse_logmel_ctx's output) ->
+ * d_hs [layers+1][B][F][hidden] fp32.  Workspace: sse_workspace_bytes_ctx(m, B, 2F, F). */
+int sse_whisper_hidden_states_from_mel_ctx(sse_model* m, const float* d_mel, int B, int frames, float* d_hs,
+                                           void* d_ws, size_t ws_bytes, void* stream);
+/* sse_whisper_embed with a context: encoder time-means over F frames, decoder states from F encoder frames. */
+int sse_whisper_embed_ctx(sse_model* m, const float* d_wave, int B, int L, int frames, const int32_t* enc_ids,
+                          int n_enc, float* d_enc_out, const int32_t* dec_ids, int n_dec, float* d_dec_out,
+                          void* d_ws, size_t ws_bytes, void* stream);
+/* sse_whisper_decoder_hidden_states with a context: d_enc [B][F][hidden] fp32 -> d_hs [decoder_layers+1][B][hidden]. */
+int sse_whisper_decoder_hidden_states_ctx(sse_model* m, const float* d_enc, int B, int frames, float* d_hs, void* d_ws,
+                                          size_t ws_bytes, void* stream);
+
 /* ---- ingest ----
  * Mono mix: torch.mean(waveform, dim=0) of load_audio (REF/WavLM_embeddings.py:103-105,
  * REF/whisper_embeddings_large.py:78-96): d_in [B][C][L] -> d_out [B][L]. */

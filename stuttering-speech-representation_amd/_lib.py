@@ -37,7 +37,11 @@ EXPORTED = ("sse_weight_floats", "sse_model_create", "sse_model_destroy", "sse_o
             "sse_mx_quantize_host", "sse_gemm_mx", "sse_pitch_shift_workspace_bytes", "sse_pitch_shift",
             "sse_set_option", "sse_get_option", "sse_embed_ragged", "sse_gemm_lnfold", "sse_check_range",
             "sse_attention", "sse_gemm_ex", "sse_attention_f8", "sse_layernorm_mx", "sse_attention_f8_mx",
-            "sse_pool_segments", "sse_pool_out_floats", "sse_embed_pooled", "sse_pool")
+            "sse_pool_segments", "sse_pool_out_floats", "sse_embed_pooled", "sse_pool",
+            "sse_whisper_context_frames", "sse_output_frames_ctx", "sse_workspace_bytes_ctx",
+            "sse_logmel_workspace_bytes_ctx", "sse_logmel_ctx", "sse_pool_out_floats_ctx", "sse_embed_pooled_ctx",
+            "sse_hidden_states_ctx", "sse_whisper_hidden_states_from_mel_ctx", "sse_whisper_embed_ctx",
+            "sse_whisper_decoder_hidden_states_ctx")
 
 
 class SSEError(RuntimeError):
@@ -159,6 +163,30 @@ def lib() -> ctypes.CDLL:
         L.sse_embed_pooled.restype = i32
         L.sse_pool.argtypes = [i32, vp, vp, i32, i32, i32, ctypes.POINTER(sse_pool_desc), vp, vp]
         L.sse_pool.restype = i32
+    if hasattr(L, "sse_embed_pooled_ctx"):   # (an earlier build loaded for an A/B has no audio context)
+        L.sse_whisper_context_frames.argtypes = [vp, i32]
+        L.sse_whisper_context_frames.restype = i32
+        L.sse_output_frames_ctx.argtypes = [vp, i32, i32]
+        L.sse_output_frames_ctx.restype = i32
+        L.sse_workspace_bytes_ctx.argtypes = [vp, i32, i32, i32]
+        L.sse_workspace_bytes_ctx.restype = sz
+        L.sse_logmel_workspace_bytes_ctx.argtypes = [i32, i32, i32]
+        L.sse_logmel_workspace_bytes_ctx.restype = sz
+        L.sse_logmel_ctx.argtypes = [vp, i32, i32, i32, i32, vp, vp, sz, vp]
+        L.sse_logmel_ctx.restype = i32
+        L.sse_pool_out_floats_ctx.argtypes = [vp, i32, i32, i32, i32, ctypes.POINTER(sse_pool_desc)]
+        L.sse_pool_out_floats_ctx.restype = sz
+        L.sse_embed_pooled_ctx.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, ctypes.POINTER(sse_pool_desc), vp, vp, sz,
+                                           vp]
+        L.sse_embed_pooled_ctx.restype = i32
+        L.sse_hidden_states_ctx.argtypes = [vp, vp, i32, i32, i32, vp, vp, sz, vp]
+        L.sse_hidden_states_ctx.restype = i32
+        L.sse_whisper_hidden_states_from_mel_ctx.argtypes = [vp, vp, i32, i32, vp, vp, sz, vp]
+        L.sse_whisper_hidden_states_from_mel_ctx.restype = i32
+        L.sse_whisper_embed_ctx.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, sz, vp]
+        L.sse_whisper_embed_ctx.restype = i32
+        L.sse_whisper_decoder_hidden_states_ctx.argtypes = [vp, vp, i32, i32, vp, vp, sz, vp]
+        L.sse_whisper_decoder_hidden_states_ctx.restype = i32
     L.sse_check_range.argtypes = [vp, vp]
     L.sse_check_range.restype = i32
     L.sse_hidden_states.argtypes = [vp, vp, i32, i32, vp, vp, sz, vp]

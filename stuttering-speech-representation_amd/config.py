@@ -18,6 +18,7 @@ C-ABI ``sse_model_create`` consumes as a flat fp32 blob.  ``csrc/sse_model.hip``
 """
 from __future__ import annotations
 
+import numbers
 from dataclasses import dataclass, field
 
 KIND_WAVLM = 0
@@ -107,6 +108,12 @@ class WhisperSpec:
     def dec_ffn_dim(self) -> int:
         return self.dec_ffn or self.ffn
 
+    def context_frames(self, n_samples: int) -> int:
+        """Smallest audio context (encoder frames, 320 samples each) that covers ``n_samples`` of audio:
+        ``min(max_positions, max(1, ceil(n_samples / 320)))``.  Pure host arithmetic (the twin of
+        sse_whisper_context_frames)."""
+        return min(self.max_positions, max(1, -(-int(n_samples) // 320)))
+
     def default_decoder_indices(self) -> list[int]:
         """``decoder_indices`` of the reference: the last three decoder hidden states."""
         n = self.decoder_layers + 1
@@ -128,6 +135,27 @@ WHISPER_LARGE_V2_DEC = WhisperSpec(decoder_layers=32, name="whisper-large-v2+dec
 WHISPER_TINY_DEC = WhisperSpec(d_model=384, layers=4, heads=6, ffn=1536, decoder_layers=4, name="whisper-tiny+decoder")
 WHISPER_SMALL_DEC = WhisperSpec(d_model=768, layers=12, heads=12, ffn=3072, decoder_layers=12,
                                 name="whisper-small+decoder")
+
+
+def resolve_frames(spec, frames, n_samples: int, lengths=None):
+    """The ``frames=`` argument of the Whisper calls (the audio context) -> encoder frames F, or
+    None for the model's own 1500.  ``frames``: None | an int in [1, max_positions] | "clip" = the smallest
+    context that covers the clip, ``context_frames(n_samples)``, or the longest of ``lengths``.  Host-only:
+    raises ValueError for anything else, and for any ``frames`` on a WavLM spec, before a library call."""
+    if frames is None:
+        return None
+    if not isinstance(spec, WhisperSpec):
+        raise ValueError(f"frames= is the Whisper audio context; {getattr(spec, 'name', spec)!r} is not a Whisper model")
+    if isinstance(frames, str):
+        if frames != "clip":
+            raise ValueError(f'frames must be None, an int or "clip", got {frames!r}')
+        n = n_samples if lengths is None else max(int(v) for v in lengths)
+        return spec.context_frames(n)
+    if isinstance(frames, bool) or not isinstance(frames, numbers.Integral):
+        raise ValueError(f'frames must be None, an int or "clip", got {frames!r}')
+    if not 1 <= int(frames) <= spec.max_positions:
+        raise ValueError(f"frames must be in [1, {spec.max_positions}], got {frames}")
+    return int(frames)
 
 
 def param_specs(spec) -> list[tuple[str, tuple]]:

@@ -248,12 +248,15 @@ def _finish_all(finish, dist, group, world: int, rank: int, start: int, stop: in
 
 
 def sse_embed_fn(model, layer_indices, *, pooling="mean", window=None, hop=None, ddof=1,
-                 valid_only=False) -> Callable[..., torch.Tensor]:
+                 valid_only=False, frames=None) -> Callable[..., torch.Tensor]:
     """embed_fn for extract_corpus backed by the HIP path (SSEModel.embed): writes into ``out``,
     ragged batches through ``lengths``.  ``pooling`` / ``window`` / ``hop`` / ``ddof`` / ``valid_only`` are
-    SSEModel.embed's pool arguments (``out`` is then [B, n_layers, (S,) n_stats*H])."""
+    SSEModel.embed's pool arguments (``out`` is then [B, n_layers, (S,) n_stats*H]); ``frames`` is its Whisper
+    audio context (an int keeps one context for the whole corpus; "clip" follows each batch's longest clip)."""
     idx = [int(i) for i in layer_indices]
     pool = dict(pool=pooling, window=window, hop=hop, ddof=ddof, valid_only=valid_only)
+    if frames is not None:   # (validated by embed on the host; a WavLM model raises ValueError there)
+        pool["frames"] = frames
 
     # no per-batch range check (it synchronises the stream and would cancel the staged copy / compute
     # overlap): fp16 / fp16x3 models are checked once, by finish(), after the rank's last batch

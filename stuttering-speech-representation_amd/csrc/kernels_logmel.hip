@@ -6,9 +6,12 @@
 //                Hann window, the 400-point real DFT as a 200-point complex FFT of the even/odd
 //                samples (Stockham radix 8 x 5 x 5 in LDS, fp32, twiddles from fp64) plus the
 //                real-FFT split, |X|^2 (201 bins, LDS) -> Slaney mel over each filter's support ->
-//                log10(max(., 1e-10)) -> logv [B][3000][n_mels], per-clip max (atomic)
-//   lm_final:    max(x, max_clip - 8), (x + 4) / 4  -> [B][n_mels][3000] (HF layout) and/or
-//                channels-last [B][3000][n_mels] in the encoder's element type (conv1 operand)
+//                log10(max(., 1e-10)) -> logv [B][nfr][n_mels], per-clip max (atomic)
+//   lm_final:    max(x, max_clip - 8), (x + 4) / 4  -> [B][n_mels][nfr] (HF layout) and/or
+//                channels-last [B][nfr][n_mels] in the encoder's element type (conv1 operand)
+// nfr = 3000 frames of the 30 s pad by default; a Whisper audio context of F encoder frames computes the first
+// nfr = 2 F only (launch argument): the grid covers ceil(nfr / 20) blocks per clip, the frames of a last partial
+// block at or past nfr are neither stored nor fed to the per-clip max, and every buffer has stride nfr.
 // HBM traffic per clip: the clip once (1.92 MB) + logv written and read back (0.96 MB each) + the
 // output; the spectrum never leaves LDS.  The filter bank is generated on device in fp64.
 #include "common.h"
@@ -167,7 +170,7 @@ SSE_DEV void fft_stage(const float2* __restrict__ x, float2* __restrict__ y, int
 __global__ __launch_bounds__(256) void lm_stft_mel_kernel(const float* __restrict__ wave, int L, int Lv0,
                                                           const int* __restrict__ lens, const float2* __restrict__ twg,
                                                           const float* __restrict__ fbp, const int2* __restrict__ sup,
-                                                          int n_mels, float* __restrict__ logv,
+                                                          int n_mels, int nfr, float* __restrict__ logv,
                                                           unsigned* __restrict__ mx) {
   __shared__ float xs[SPAN];
   __shared__ float2 tw[3 * NZ];   // W_200^k | W_400^k | Hann pairs
@@ -230,6 +233,7 @@ __global__ __launch_bounds__(256) void lm_stft_mel_kernel(const float* __restric
       P[wv][k] = px;
     }
     wsync();
+    if (t0 + fr >= nfr) continue;   // (wave-uniform) last partial block: no store, no max past nfr
     for (int m = lane; m < n_mels; m += 64) {
       // in-order fma chain over the filter's support: bit-identical to the dense 201-bin chain (the
       // other terms are fma(0, P, acc) = acc)
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(256) void lm_stft_mel_kernel(const float* __restric
         acc = fmaf(fw[m * MAXSUP + i], P[wv][k], acc);
       }
       const float v = log10f(fmaxf(acc, 1e-10f));
-      logv[((long long)b * NFR + t0 + fr) * n_mels + m] = v;
+      logv[((long long)b * nfr + t0 + fr) * n_mels + m] = v;
       lmax = fmaxf(lmax, v);
     }
   }
@@ -355,12 +359,11 @@ SSE_DEV void fft_stage4(float2* __restrict__ z, int Ns, const float2* __restrict
 // Block = one 20-frame chunk (a persistent form walking chunks with the next chunk's samples prefetched
 // into registers measured slower: 0.78 vs 0.61 ms for 128 x 30 s -- its per-chunk block barriers
 // serialise the waves that separate blocks on a CU keep out of phase).
-constexpr int LM_CPC = NFR / MEL_FR;   // chunks per clip
 __global__ __launch_bounds__(64 * LM_W) void lm_stft_mel4_kernel(const float* __restrict__ wave, int B, int L, int Lv0,
                                                                  const int* __restrict__ lens,
                                                                  const float2* __restrict__ twg,
                                                                  const float* __restrict__ fbp,
-                                                                 const int2* __restrict__ sup, int n_mels,
+                                                                 const int2* __restrict__ sup, int n_mels, int nfr,
                                                                  float* __restrict__ logv, unsigned* __restrict__ mx) {
   constexpr int NTH = 64 * LM_W;
   // dynamic LDS (47.7 KB at 80 mels: three blocks per CU): the frame buffers, whose first 13.8 KB also
@@ -378,12 +381,13 @@ __global__ __launch_bounds__(64 * LM_W) void lm_stft_mel4_kernel(const float* __
   static_assert(LM_F == 4, "mel task split m = task >> 2");
   const float2* win = tw + 2 * NZ;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int nch = B * LM_CPC;
+  const int cpc = (nfr + MEL_FR - 1) / MEL_FR;   // chunks per clip (150 for the full 3000 frames)
+  const int nch = B * cpc;
   constexpr int NX = (SPAN + NTH - 1) / NTH;
   float xr[NX];
   // samples of chunk c (zero-pad / truncate to 480000, reflect-pad 200) into registers
   auto load_chunk = [&](int c) {
-    const int b = c / LM_CPC, t0 = (c - b * LM_CPC) * MEL_FR;
+    const int b = c / cpc, t0 = (c - b * cpc) * MEL_FR;
     const int Lv = lens ? min(max(lens[b], 0), Lv0) : Lv0;   // clamped to [0, min(L, NS)]
     const float* xw = wave + (long long)b * L;
     #pragma unroll
@@ -431,7 +435,7 @@ __global__ __launch_bounds__(64 * LM_W) void lm_stft_mel4_kernel(const float* __
   float2* z = zbuf[wv];
   const int fr0 = wv * LM_F;   // the wave's first frame within the chunk
   {
-    const int b = c / LM_CPC, t0 = (c - b * LM_CPC) * MEL_FR;
+    const int b = c / cpc, t0 = (c - b * cpc) * MEL_FR;
     #pragma unroll
     for (int u = 0; u < NX; ++u) {
       const int i = threadIdx.x + u * NTH;
@@ -505,11 +509,12 @@ __global__ __launch_bounds__(64 * LM_W) void lm_stft_mel4_kernel(const float* __
     for (int task = lane; task < LM_F * n_mels; task += 64) {
       const int m = task >> 2, f = task & (LM_F - 1);
       const float* Pf = P + f * PST + fs[m];
+      if (t0 + fr0 + f >= nfr) continue;   // last partial chunk: no store, no max past nfr
       const int n = fsn[m];
       float acc = 0.f;
       for (int i = 0; i < n; ++i) acc = fmaf(fwt[i * n_mels + m], Pf[i], acc);
       const float v = log10f(fmaxf(acc, 1e-10f));
-      logv[((long long)b * NFR + t0 + fr0 + f) * n_mels + m] = v;
+      logv[((long long)b * nfr + t0 + fr0 + f) * n_mels + m] = v;
       lmax = fmaxf(lmax, v);
     }
     lmax = wave_max(lmax);
@@ -518,37 +523,39 @@ __global__ __launch_bounds__(64 * LM_W) void lm_stft_mel4_kernel(const float* __
 }
 
 // 64 frames x n_mels per block: channels-last output straight through (coalesced), the HF layout
-// [B][n_mels][3000] through an LDS transpose so its 64-frame rows are coalesced too
+// [B][n_mels][nfr] through an LDS transpose so its 64-frame rows are coalesced too
 constexpr int FIN_T = 64;
 template <typename TO>
 __global__ __launch_bounds__(256) void lm_final_kernel(const float* __restrict__ logv, const unsigned* __restrict__ mx,
-                                                       int n_mels, float* __restrict__ out_hf, TO* __restrict__ out_cl) {
+                                                       int n_mels, int nfr, float* __restrict__ out_hf,
+                                                       TO* __restrict__ out_cl) {
   __shared__ float tile[LM_MAXMEL][FIN_T + 1];
   const int b = blockIdx.y, t0 = blockIdx.x * FIN_T;
-  const int nt = NFR - t0 < FIN_T ? NFR - t0 : FIN_T;
+  const int nt = nfr - t0 < FIN_T ? nfr - t0 : FIN_T;
   const float cl = unord_f32(mx[b]) - 8.0f;
-  const float* src = logv + ((long long)b * NFR + t0) * n_mels;
+  const float* src = logv + ((long long)b * nfr + t0) * n_mels;
   for (int i = threadIdx.x; i < nt * n_mels; i += 256) {
     const int t = i / n_mels, m = i - t * n_mels;
     const float v = (fmaxf(src[i], cl) + 4.0f) / 4.0f;
-    if (out_cl) out_cl[((long long)b * NFR + t0) * n_mels + i] = from_f32<TO>(v);
+    if (out_cl) out_cl[((long long)b * nfr + t0) * n_mels + i] = from_f32<TO>(v);
     tile[m][t] = v;
   }
   if (!out_hf) return;
   __syncthreads();
   for (int i = threadIdx.x; i < n_mels * FIN_T; i += 256) {
     const int m = i / FIN_T, t = i - m * FIN_T;
-    if (t < nt) out_hf[((long long)b * n_mels + m) * NFR + t0 + t] = tile[m][t];
+    if (t < nt) out_hf[((long long)b * n_mels + m) * nfr + t0 + t] = tile[m][t];
   }
 }
 
 template <typename TO>
-__global__ __launch_bounds__(256) void mel_to_cl_kernel(const float* __restrict__ mel, int n_mels, TO* __restrict__ out) {
+__global__ __launch_bounds__(256) void mel_to_cl_kernel(const float* __restrict__ mel, int n_mels, int nfr,
+                                                        TO* __restrict__ out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
-  if (i >= (long long)NFR * n_mels) return;
+  if (i >= (long long)nfr * n_mels) return;
   const int t = (int)(i / n_mels), m = (int)(i - (long long)t * n_mels);
-  out[(long long)b * NFR * n_mels + i] = from_f32<TO>(mel[((long long)b * n_mels + m) * NFR + t]);
+  out[(long long)b * nfr * n_mels + i] = from_f32<TO>(mel[((long long)b * n_mels + m) * nfr + t]);
 }
 
 __global__ __launch_bounds__(256) void normalize_apply_kernel(const float* __restrict__ x, int L,
@@ -562,35 +569,41 @@ __global__ __launch_bounds__(256) void normalize_apply_kernel(const float* __res
 }  // namespace
 
 template <typename TO>
-int launch_mel_to_cl(const float* mel_hf, int B, int n_mels, TO* out_cl, hipStream_t s) {
-  hipLaunchKernelGGL((mel_to_cl_kernel<TO>), dim3((NFR * n_mels + 255) / 256, B), dim3(256), 0, s, mel_hf, n_mels,
+int launch_mel_to_cl(const float* mel_hf, int B, int n_mels, int nfr, TO* out_cl, hipStream_t s) {
+  if (B <= 0 || nfr <= 0 || nfr > NFR) return -1;
+  hipLaunchKernelGGL((mel_to_cl_kernel<TO>), dim3((nfr * n_mels + 255) / 256, B), dim3(256), 0, s, mel_hf, n_mels, nfr,
                      out_cl);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
-template int launch_mel_to_cl<float>(const float*, int, int, float*, hipStream_t);
-template int launch_mel_to_cl<bf16>(const float*, int, int, bf16*, hipStream_t);
+template int launch_mel_to_cl<float>(const float*, int, int, int, float*, hipStream_t);
+template int launch_mel_to_cl<bf16>(const float*, int, int, int, bf16*, hipStream_t);
 
 int launch_normalize_apply(const float* x, int B, int L, const float* st, float* y, hipStream_t s) {
   hipLaunchKernelGGL(normalize_apply_kernel, dim3((L + 255) / 256, B), dim3(256), 0, s, x, L, st, y);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-size_t logmel_workspace_bytes(int B, int n_mels) {
+size_t logmel_workspace_bytes(int B, int n_mels, int nfr) {
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  return al((size_t)3 * NZ * 8) + al((size_t)NF * n_mels * 4) + al((size_t)B * NFR * n_mels * 4) + al((size_t)B * 4) +
+  return al((size_t)3 * NZ * 8) + al((size_t)NF * n_mels * 4) + al((size_t)B * nfr * n_mels * 4) + al((size_t)B * 4) +
          al((size_t)n_mels * 8) + 2 * al((size_t)n_mels * MAXSUP * 4);
 }
 
 template <typename TO>
-int launch_logmel(const float* x, int B, int L, int n_mels, float* out_hf, TO* out_cl, void* ws, size_t ws_bytes,
-                  hipStream_t s, const int* lens) {
+int launch_logmel(const float* x, int B, int L, int n_mels, int nfr, float* out_hf, TO* out_cl, void* ws,
+                  size_t ws_bytes, hipStream_t s, const int* lens) {
   if (B <= 0 || L <= 0 || n_mels < 64 || n_mels > LM_MAXMEL) return -1;   // Whisper: 80 or 128 mels
-  if (ws_bytes < logmel_workspace_bytes(B, n_mels)) return -4;
+  if (nfr <= 0 || nfr > NFR || nfr % 2) return -1;                        // two mel frames per encoder frame
+  if (ws_bytes < logmel_workspace_bytes(B, n_mels, nfr)) return -4;
+  // the clip is cut at the context's last sample (HOP nfr = 320 per encoder frame; 480000 at the full 3000 frames):
+  // the last frames' windows reach 40 samples past it and must see the zero pad there, not the clip
+  const int Lv0 = L < HOP * nfr ? L : HOP * nfr;
+  const int cpc = (nfr + MEL_FR - 1) / MEL_FR;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   char* p = (char*)ws;
   float2* tw = (float2*)p; p += al((size_t)3 * NZ * 8);
   float* fb = (float*)p; p += al((size_t)NF * n_mels * 4);
-  float* logv = (float*)p; p += al((size_t)B * NFR * n_mels * 4);
+  float* logv = (float*)p; p += al((size_t)B * nfr * n_mels * 4);
   unsigned* mx = (unsigned*)p; p += al((size_t)B * 4);
   int2* sup = (int2*)p; p += al((size_t)n_mels * 8);
   float* fbp = (float*)p; p += al((size_t)n_mels * MAXSUP * 4);
@@ -599,18 +612,19 @@ int launch_logmel(const float* x, int B, int L, int n_mels, float* out_hf, TO* o
   hipLaunchKernelGGL(lm_filters_kernel, dim3((NF * n_mels + 255) / 256), dim3(256), 0, s, fb, n_mels);
   hipLaunchKernelGGL(lm_support_kernel, dim3(n_mels), dim3(256), 0, s, fb, n_mels, sup, fbp, fbt);
   if (sse_opt(OPT_LOGMEL_V1))
-    hipLaunchKernelGGL(lm_stft_mel_kernel, dim3(NFR / MEL_FR, B), dim3(256), 0, s, x, L, L < NS ? L : NS, lens, tw, fbp,
-                       sup, n_mels, logv, mx);
+    hipLaunchKernelGGL(lm_stft_mel_kernel, dim3(cpc, B), dim3(256), 0, s, x, L, Lv0, lens, tw, fbp, sup, n_mels, nfr,
+                       logv, mx);
   else
   {
     const size_t lds = (size_t)LM_W * LM_F * NZ * 8 + 3 * NZ * 8 + (size_t)MAXSUP * n_mels * 4 + (size_t)n_mels * 8;
-    hipLaunchKernelGGL(lm_stft_mel4_kernel, dim3(B * LM_CPC), dim3(64 * LM_W), lds, s, x, B, L, L < NS ? L : NS, lens, tw,
-                       fbt, sup, n_mels, logv, mx);
+    hipLaunchKernelGGL(lm_stft_mel4_kernel, dim3(B * cpc), dim3(64 * LM_W), lds, s, x, B, L, Lv0, lens, tw, fbt, sup,
+                       n_mels, nfr, logv, mx);
   }
-  hipLaunchKernelGGL((lm_final_kernel<TO>), dim3((NFR + FIN_T - 1) / FIN_T, B), dim3(256), 0, s, logv, mx, n_mels,
+  hipLaunchKernelGGL((lm_final_kernel<TO>), dim3((nfr + FIN_T - 1) / FIN_T, B), dim3(256), 0, s, logv, mx, n_mels, nfr,
                      out_hf, out_cl);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
-template int launch_logmel<float>(const float*, int, int, int, float*, float*, void*, size_t, hipStream_t,
+template int launch_logmel<float>(const float*, int, int, int, int, float*, float*, void*, size_t, hipStream_t,
                                   const int*);
-template int launch_logmel<bf16>(const float*, int, int, int, float*, bf16*, void*, size_t, hipStream_t, const int*);
+template int launch_logmel<bf16>(const float*, int, int, int, int, float*, bf16*, void*, size_t, hipStream_t,
+                                 const int*);

@@ -733,22 +733,30 @@ struct WhisperWs {
   size_t fr;       // valid-frame pooling (sse_pool_desc.valid_only): per-clip encoder frame counts [B]
 };
 
-WhisperWs whisper_plan(const sse_model* m, int B, Plan& p) {
+// T: encoder frames of the call (the audio context; cfg.max_positions = 1500 by default): every B * T term scales
+WhisperWs whisper_plan(const sse_model* m, int B, int T, Plan& p) {
   const sse_cfg& c = m->cfg;
   const size_t es = m->bf() ? 2 : 4;
-  const int D = c.hidden, T = c.max_positions, T2 = 2 * T;
+  const int D = c.hidden, T2 = 2 * T;
   const size_t M = (size_t)B * T;
   WhisperWs w;
   w.zero = p.add(256);
-  w.lm = p.add(logmel_workspace_bytes(B, c.n_mels));
+  w.lm = p.add(logmel_workspace_bytes(B, c.n_mels, T2));
   w.mel = p.add((size_t)B * T2 * c.n_mels * es);
   w.h1 = p.add((size_t)B * T2 * D * es);
   const size_t ex = m->x3() ? 6 : es;   // GEMM operands: tripled f16 rows [hi | lo' | hi] on the fp16x3 path
   w.x = p.add(M * D * es);   // residual stream: bf16 on the bf16 / MX-fp8 paths, fp32 on the fp32 path
-  w.xb = p.add(M * D * ex);
+  // SSE_DTYPE_FP8: xb / ff (and ctx with f8_oproj) also hold an MX-fp8 operand, M K e4m3 bytes followed by its scales
+  // in the GEMM's A layout, which is padded to 256-row tiles (mx_scale_bytes: 8 K bytes per tile).  The bf16 size
+  // 2 M K covers that from M = 8 rows on; a context of a few frames on one clip has fewer
+  auto opnd = [&](size_t K) {
+    const size_t plain = M * K * ex, mxb = m->mx() ? M * K + (size_t)mx_scale_bytes((long long)M, (int)K) : 0;
+    return plain > mxb ? plain : mxb;
+  };
+  w.xb = p.add(opnd(D));
   w.qkv = p.add(M * 3 * D * es);
-  w.ctx = p.add(M * D * ex);
-  w.ff = p.add(M * (size_t)c.ffn * ex);
+  w.ctx = p.add(opnd(D));
+  w.ff = p.add(opnd(c.ffn));
   w.xf = p.add(M * D * 4);
   w.vam = m->mx() ? p.add((size_t)B * D * 4) : 0;
   w.p1 = w.p2 = 0;
@@ -1292,15 +1300,16 @@ int wavlm_forward_x3(sse_model* m, const float* wave, int B, int L, const Sink& 
 }
 
 // The reference's 1-token decoder pass (REF/whisper_embeddings_large.py:257-262): input id 0 at
-// position 0, cross-attending to the encoder's last_hidden_state enc [B*Tq][D] (type T).  Rows
+// position 0, cross-attending to the encoder's last_hidden_state enc [B*Tq][D] (type T; Tq = the call's encoder
+// frames, cfg.max_positions or the audio context).  Rows
 // are clips (M = B); the K|V projection of the encoder output is the one large GEMM per layer.
 // hidden_states[i] = input of layer i, hidden_states[L] = final-LN output
 // (HF/models/whisper/modeling_whisper.py:739-790, HF/utils/output_capturing.py:268-279).
 template <typename T>
-int whisper_decoder(sse_model* m, const T* enc, int B, const Sink& sink, char* ws, const WhisperWs& w,
+int whisper_decoder(sse_model* m, const T* enc, int B, int Tq, const Sink& sink, char* ws, const WhisperWs& w,
                     hipStream_t s) {
   const sse_cfg& c = m->cfg;
-  const int D = c.hidden, Fd = c.dec_ffn, nh = c.heads, Tq = c.max_positions;
+  const int D = c.hidden, Fd = c.dec_ffn, nh = c.heads;
   const float eps = c.ln_eps;
   void* zero = ws + w.zero;
   float* x = (float*)(ws + w.dx);
@@ -1354,32 +1363,32 @@ int whisper_decoder(sse_model* m, const T* enc, int B, const Sink& sink, char* w
 
 // Valid-frame pooling (sse_pool_desc.valid_only): the encoder sink pools each clip's first
 // min(Tq, ceil(len / 320)) frames, counted on the device into the workspace; the forward is unchanged.
-int whisper_valid_frames(const sse_model* m, Sink& sink, const int* lens, int B, int L, int* tq, hipStream_t s) {
+int whisper_valid_frames(Sink& sink, const int* lens, int B, int L, int Tq, int* tq, hipStream_t s) {
   if (!sink.valid_only || !sink.pooled) return 0;
-  RC(launch_whisper_frames(lens, B, L, m->cfg.max_positions, tq, s));
+  RC(launch_whisper_frames(lens, B, L, Tq, tq, s));
   sink.tlen = tq;
   return 0;
 }
 
 template <typename T>
-int whisper_forward(sse_model* m, const float* wave, int B, int L, const Sink& sink_in, char* ws, hipStream_t s,
+int whisper_forward(sse_model* m, const float* wave, int B, int L, int Tq, const Sink& sink_in, char* ws, hipStream_t s,
                     const float* mel_hf = nullptr, const Sink* dsink = nullptr, const int* lens = nullptr) {
   const sse_cfg& c = m->cfg;
   Plan p;
-  const WhisperWs w = whisper_plan(m, B, p);
+  const WhisperWs w = whisper_plan(m, B, Tq, p);
   Sink sink = sink_in;
-  RC(whisper_valid_frames(m, sink, lens, B, L, (int*)(ws + w.fr), s));
-  const int D = c.hidden, F = c.ffn, nh = c.heads, Tq = c.max_positions, T2 = 2 * Tq, nm = c.n_mels;
+  RC(whisper_valid_frames(sink, lens, B, L, Tq, (int*)(ws + w.fr), s));
+  const int D = c.hidden, F = c.ffn, nh = c.heads, T2 = 2 * Tq, nm = c.n_mels;
   const int M = B * Tq;
   const float eps = c.ln_eps;
   void* zero = ws + w.zero;
   if (hipMemsetAsync(zero, 0, 256, s) != hipSuccess) return SSE_ERR_HIP;
   T* mel = (T*)(ws + w.mel);
   if (mel_hf)
-    RC(launch_mel_to_cl<T>(mel_hf, B, nm, mel, s));
+    RC(launch_mel_to_cl<T>(mel_hf, B, nm, T2, mel, s));
   else
-    RC(prof(m, s, "logmel", B * 3000.0 * 5.0 * 200 * 7.64, (double)B * (480000.0 * 4 + 3000.0 * nm * (8.0 + sizeof(T))),
-            [&] { return launch_logmel<T>(wave, B, L, nm, nullptr, mel, ws + w.lm, logmel_workspace_bytes(B, nm), s,
+    RC(prof(m, s, "logmel", B * (double)T2 * 5.0 * 200 * 7.64, (double)B * (160.0 * T2 * 4 + (double)T2 * nm * (8.0 + sizeof(T))),
+            [&] { return launch_logmel<T>(wave, B, L, nm, T2, nullptr, mel, ws + w.lm, logmel_workspace_bytes(B, nm, T2), s,
                                           lens); }));
   T* h1 = (T*)(ws + w.h1);
   // residual stream in the path's element type: the bf16 / MX-fp8 paths keep it in bf16 (the residual
@@ -1421,7 +1430,9 @@ int whisper_forward(sse_model* m, const float* wave, int B, int L, const Sink& s
   unsigned char* fq_s = fq + (size_t)M * F;
   // fp8 attention (default on the MX path): Q | K e4m3 [M][2D] | V bf16 [M][D] | Q | K scales [M][2D / 32] in
   // the QKV space ([M][3D] bf16 = 6D bytes per row)
-  const bool f8attn = mx && !sse_opt(OPT_FP8_ATTN_BF16);
+  // (an audio context under 64 frames keeps the bf16 QKV output and the bf16 attention: the fused QKV epilogue
+  // reduces max |V| over 64-row blocks that span at most two clips, launch_gemm8_mx: vamax_rows >= 64)
+  const bool f8attn = mx && !sse_opt(OPT_FP8_ATTN_BF16) && Tq >= 64;
   // MX-fp8 out-projection (round 6, opt-in f8_oproj = 1): the attention writes its output as MX-fp8 (e4m3 +
   // A-layout scales) into ctx's space and the out-projection runs on the MX GEMM with the residual.  Not the
   // default: one more e4m3 rounding per layer takes Whisper-large-v2 (B = 128, 32 layers) from 0.066 to 0.083
@@ -1543,7 +1554,7 @@ int whisper_forward(sse_model* m, const float* wave, int B, int L, const Sink& s
   RC((launch_layernorm<R, T>(x, m->ptr<float>(m->enc_ln_w), m->ptr<float>(m->enc_ln_b), M, D, eps, ACT_NONE, xf,
                              dsink ? xb : (T*)nullptr, s)));
   RC(sink.emit(c.layers, xf));
-  if (dsink) RC(whisper_decoder<T>(m, xb, B, *dsink, ws, w, s));
+  if (dsink) RC(whisper_decoder<T>(m, xb, B, Tq, *dsink, ws, w, s));
   return 0;
 }
 
@@ -1552,25 +1563,25 @@ int whisper_forward(sse_model* m, const float* wave, int B, int L, const Sink& s
 // (fp32 softmax, f16 matrix-core products of split operands) writes the out-projection's tripled operand,
 // fc1's epilogue the fc2 operand with erf-GELU; log-mel, conv1 / conv2 (exact-f32 MFMA, 0.7 % of the FLOPs),
 // the residual stream and the 1-token decoder stay fp32.
-int whisper_forward_x3(sse_model* m, const float* wave, int B, int L, const Sink& sink_in, char* ws, hipStream_t s,
-                       const float* mel_hf, const Sink* dsink, const int* lens) {
+int whisper_forward_x3(sse_model* m, const float* wave, int B, int L, int Tq, const Sink& sink_in, char* ws,
+                       hipStream_t s, const float* mel_hf, const Sink* dsink, const int* lens) {
   const sse_cfg& c = m->cfg;
   Plan p;
-  const WhisperWs w = whisper_plan(m, B, p);
+  const WhisperWs w = whisper_plan(m, B, Tq, p);
   Sink sink = sink_in;
-  RC(whisper_valid_frames(m, sink, lens, B, L, (int*)(ws + w.fr), s));
-  const int D = c.hidden, F = c.ffn, nh = c.heads, Tq = c.max_positions, T2 = 2 * Tq, nm = c.n_mels;
+  RC(whisper_valid_frames(sink, lens, B, L, Tq, (int*)(ws + w.fr), s));
+  const int D = c.hidden, F = c.ffn, nh = c.heads, T2 = 2 * Tq, nm = c.n_mels;
   const int M = B * Tq;
   const float eps = c.ln_eps;
   void* zero = ws + w.zero;
   if (hipMemsetAsync(zero, 0, 256, s) != hipSuccess) return SSE_ERR_HIP;
   float* mel = (float*)(ws + w.mel);
   if (mel_hf)
-    RC(launch_mel_to_cl<float>(mel_hf, B, nm, mel, s));
+    RC(launch_mel_to_cl<float>(mel_hf, B, nm, T2, mel, s));
   else
-    RC(prof(m, s, "logmel", B * 3000.0 * 5.0 * 200 * 7.64, (double)B * (480000.0 * 4 + 3000.0 * nm * 12.0),
-            [&] { return launch_logmel<float>(wave, B, L, nm, nullptr, mel, ws + w.lm, logmel_workspace_bytes(B, nm), s,
-                                              lens); }));
+    RC(prof(m, s, "logmel", B * (double)T2 * 5.0 * 200 * 7.64, (double)B * (160.0 * T2 * 4 + (double)T2 * nm * 12.0),
+            [&] { return launch_logmel<float>(wave, B, L, nm, T2, nullptr, mel, ws + w.lm,
+                                              logmel_workspace_bytes(B, nm, T2), s, lens); }));
   float* h1 = (float*)(ws + w.h1);
   float* x = (float*)(ws + w.x);
   f16* xb = (f16*)(ws + w.xb);
@@ -1630,7 +1641,7 @@ int whisper_forward_x3(sse_model* m, const float* wave, int B, int L, const Sink
   RC((launch_layernorm<float, float>(x, m->ptr<float>(m->enc_ln_w), m->ptr<float>(m->enc_ln_b), M, D, eps, ACT_NONE,
                                      xf, (float*)nullptr, s)));
   RC(sink.emit(c.layers, xf));
-  if (dsink) RC(whisper_decoder<float>(m, xf, B, *dsink, ws, w, s));
+  if (dsink) RC(whisper_decoder<float>(m, xf, B, Tq, *dsink, ws, w, s));
   return 0;
 }
 
@@ -1658,7 +1669,7 @@ size_t wavlm_ws(const sse_model* m, int B, int L) {
 }
 
 int forward_one(sse_model* m, const float* d_in, int B, int L, const Sink& sink, void* d_ws, hipStream_t s,
-                bool from_mel, const Sink* dsink, const int* lens);
+                bool from_mel, const Sink* dsink, const int* lens, int ctx = 0);
 
 int split_forward(sse_model* m, const float* d_in, int B, int L, const Sink& sink, char* ws, hipStream_t s,
                   const int* lens) {
@@ -1749,13 +1760,18 @@ size_t split_ws_bytes(const sse_model* m, int B, int L) {
 }
 
 int forward_any(sse_model* m, const float* d_in, int B, int L, const Sink& sink, void* d_ws, size_t ws_bytes,
-                hipStream_t s, bool from_mel, const Sink* dsink, const int* lens);
+                hipStream_t s, bool from_mel, const Sink* dsink, const int* lens, int ctx);
+
+// Whisper audio context: ctx = 0 is the model's own frame count (cfg.max_positions, every call without a context),
+// otherwise the encoder frames F of this call, validated by the entry point (1 <= F <= cfg.max_positions, Whisper)
+inline int whisper_ctx(const sse_model* m, int ctx) { return ctx > 0 ? ctx : m->cfg.max_positions; }
+size_t workspace_bytes(const sse_model* m, int B, int L, int ctx);
 
 // fp16-range dtypes: every value the call wrote is scanned and the handle's range flag raised on a
 // non-finite one (sse_check_range reports it)
 int forward(sse_model* m, const float* d_in, int B, int L, const Sink& sink, void* d_ws, size_t ws_bytes,
-            hipStream_t s, bool from_mel = false, const Sink* dsink = nullptr, const int* lens = nullptr) {
-  const int rc = forward_any(m, d_in, B, L, sink, d_ws, ws_bytes, s, from_mel, dsink, lens);
+            hipStream_t s, bool from_mel = false, const Sink* dsink = nullptr, const int* lens = nullptr, int ctx = 0) {
+  const int rc = forward_any(m, d_in, B, L, sink, d_ws, ws_bytes, s, from_mel, dsink, lens, ctx);
   if (rc || !(m->h16() || m->x3())) return rc;
   int* flag = (int*)(m->dmem + m->status);
   if (sink.pooled) RC(launch_finite_flag(sink.pooled, (long long)B * sink.n_ids * (long long)sink.slot(), flag, s));
@@ -1764,9 +1780,9 @@ int forward(sse_model* m, const float* d_in, int B, int L, const Sink& sink, voi
 }
 
 int forward_any(sse_model* m, const float* d_in, int B, int L, const Sink& sink, void* d_ws, size_t ws_bytes,
-                hipStream_t s, bool from_mel, const Sink* dsink, const int* lens) {
+                hipStream_t s, bool from_mel, const Sink* dsink, const int* lens, int ctx) {
   if (!m || !d_in || B <= 0 || L <= 0) return SSE_ERR_INVALID;
-  if (ws_bytes < sse_workspace_bytes(m, B, L)) return SSE_ERR_WORKSPACE;
+  if (ws_bytes < workspace_bytes(m, B, L, ctx)) return SSE_ERR_WORKSPACE;
   if (!from_mel && !dsink && split_applies(m, B, &sink)) {
     if (wavlm_frames(m->cfg, L, nullptr) <= 0) return SSE_ERR_INVALID;
     int dev = -1;
@@ -1776,11 +1792,11 @@ int forward_any(sse_model* m, const float* d_in, int B, int L, const Sink& sink,
     if (dev != m->device) (void)hipSetDevice(dev);
     return rc;
   }
-  return forward_one(m, d_in, B, L, sink, d_ws, s, from_mel, dsink, lens);
+  return forward_one(m, d_in, B, L, sink, d_ws, s, from_mel, dsink, lens, ctx);
 }
 
 int forward_one(sse_model* m, const float* d_in, int B, int L, const Sink& sink, void* d_ws, hipStream_t s,
-                bool from_mel, const Sink* dsink, const int* lens) {
+                bool from_mel, const Sink* dsink, const int* lens, int ctx) {
   if (m->cfg.kind == SSE_KIND_WAVLM && wavlm_frames(m->cfg, L, nullptr) <= 0) return SSE_ERR_INVALID;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return SSE_ERR_HIP;
@@ -1793,16 +1809,41 @@ int forward_one(sse_model* m, const float* d_in, int B, int L, const Sink& sink,
          : m->h16() ? wavlm_forward<f16>(m, d_in, B, L, sink, (char*)d_ws, s, lens)
                     : wavlm_forward<float>(m, d_in, B, L, sink, (char*)d_ws, s, lens);
   else if (m->x3())
-    rc = whisper_forward_x3(m, d_in, B, L, sink, (char*)d_ws, s, from_mel ? d_in : nullptr, dsink, lens);
+    rc = whisper_forward_x3(m, d_in, B, L, whisper_ctx(m, ctx), sink, (char*)d_ws, s, from_mel ? d_in : nullptr, dsink,
+                            lens);
   else
-    rc = m->bf() ? whisper_forward<bf16>(m, d_in, B, L, sink, (char*)d_ws, s, from_mel ? d_in : nullptr, dsink, lens)
-                 : whisper_forward<float>(m, d_in, B, L, sink, (char*)d_ws, s, from_mel ? d_in : nullptr, dsink, lens);
+    rc = m->bf() ? whisper_forward<bf16>(m, d_in, B, L, whisper_ctx(m, ctx), sink, (char*)d_ws, s,
+                                         from_mel ? d_in : nullptr, dsink, lens)
+                 : whisper_forward<float>(m, d_in, B, L, whisper_ctx(m, ctx), sink, (char*)d_ws, s,
+                                          from_mel ? d_in : nullptr, dsink, lens);
   if (dev != m->device) (void)hipSetDevice(dev);
   return rc;
 }
 
-int hs_frames(const sse_model* m, int L) {
-  return m->cfg.kind == SSE_KIND_WAVLM ? wavlm_frames(m->cfg, L, nullptr) : m->cfg.max_positions;
+int hs_frames(const sse_model* m, int L, int ctx = 0) {
+  return m->cfg.kind == SSE_KIND_WAVLM ? wavlm_frames(m->cfg, L, nullptr) : whisper_ctx(m, ctx);
+}
+
+size_t workspace_bytes(const sse_model* m, int B, int L, int ctx) {
+  if (!m || B <= 0 || L <= 0) return 0;
+  Plan p;
+  if (m->cfg.kind == SSE_KIND_WAVLM) {
+    if (wavlm_frames(m->cfg, L, nullptr) <= 0) return 0;
+    const size_t one = wavlm_ws(m, B, L);
+    if (split_applies(m, B, nullptr)) {   // the parts' workspaces (split_forward); also covers one stream
+      const size_t parts = split_ws_bytes(m, B, L);
+      return parts > one ? parts : one;
+    }
+    return one;
+  } else {
+    whisper_plan(m, B, whisper_ctx(m, ctx), p);
+  }
+  return p.total;
+}
+
+// a context-taking entry point's F: Whisper handles only, 1 <= F <= cfg.max_positions
+bool ctx_ok(const sse_model* m, int frames) {
+  return m && m->cfg.kind == SSE_KIND_WHISPER && frames >= 1 && frames <= m->cfg.max_positions;
 }
 
 }  // namespace
@@ -1950,21 +1991,21 @@ int sse_output_frames(const sse_model* m, int L) {
   return hs_frames(m, L);
 }
 
-size_t sse_workspace_bytes(const sse_model* m, int B, int L) {
-  if (!m || B <= 0 || L <= 0) return 0;
-  Plan p;
-  if (m->cfg.kind == SSE_KIND_WAVLM) {
-    if (wavlm_frames(m->cfg, L, nullptr) <= 0) return 0;
-    const size_t one = wavlm_ws(m, B, L);
-    if (split_applies(m, B, nullptr)) {   // the parts' workspaces (split_forward); also covers one stream
-      const size_t parts = split_ws_bytes(m, B, L);
-      return parts > one ? parts : one;
-    }
-    return one;
-  } else {
-    whisper_plan(m, B, p);
-  }
-  return p.total;
+size_t sse_workspace_bytes(const sse_model* m, int B, int L) { return workspace_bytes(m, B, L, 0); }
+
+size_t sse_workspace_bytes_ctx(const sse_model* m, int B, int L, int frames) {
+  return ctx_ok(m, frames) ? workspace_bytes(m, B, L, frames) : 0;
+}
+
+int sse_output_frames_ctx(const sse_model* m, int L, int frames) {
+  if (!ctx_ok(m, frames) || L <= 0) return SSE_ERR_INVALID;
+  return frames;
+}
+
+int sse_whisper_context_frames(const sse_model* m, int n_samples) {
+  if (!m || m->cfg.kind != SSE_KIND_WHISPER) return SSE_ERR_INVALID;
+  const int f = n_samples > 0 ? (int)(((long long)n_samples + 319) / 320) : 1;
+  return f < m->cfg.max_positions ? f : m->cfg.max_positions;
 }
 
 size_t sse_logmel_workspace_bytes(int B, int n_mels) { return logmel_workspace_bytes(B, n_mels); }
@@ -1972,7 +2013,20 @@ size_t sse_logmel_workspace_bytes(int B, int n_mels) { return logmel_workspace_b
 int sse_logmel(const float* d_wave, int B, int L, int n_mels, float* d_mel, void* d_ws, size_t ws_bytes,
                void* stream) {
   if (!d_wave || !d_mel || !d_ws) return SSE_ERR_INVALID;
-  return launch_logmel<float>(d_wave, B, L, n_mels, d_mel, (float*)nullptr, d_ws, ws_bytes, (hipStream_t)stream);
+  return launch_logmel<float>(d_wave, B, L, n_mels, LM_NFR, d_mel, (float*)nullptr, d_ws, ws_bytes,
+                              (hipStream_t)stream);
+}
+
+size_t sse_logmel_workspace_bytes_ctx(int B, int n_mels, int frames) {
+  if (B <= 0 || frames < 1 || 2 * frames > LM_NFR) return 0;
+  return logmel_workspace_bytes(B, n_mels, 2 * frames);
+}
+
+int sse_logmel_ctx(const float* d_wave, int B, int L, int n_mels, int frames, float* d_mel, void* d_ws,
+                   size_t ws_bytes, void* stream) {
+  if (!d_wave || !d_mel || !d_ws || frames < 1 || 2 * frames > LM_NFR) return SSE_ERR_INVALID;
+  return launch_logmel<float>(d_wave, B, L, n_mels, 2 * frames, d_mel, (float*)nullptr, d_ws, ws_bytes,
+                              (hipStream_t)stream);
 }
 
 int sse_check_range(sse_model* m, void* stream) {
@@ -2026,13 +2080,14 @@ size_t sse_pool_out_floats(const sse_model* m, int B, int L, int n_layers, const
   return (size_t)B * n_layers * pool_segments(T, d->win, d->hop) * pool_nstats(d) * m->cfg.hidden;
 }
 
-int sse_embed_pooled(sse_model* m, const float* d_in, const int32_t* d_lengths, int B, int L, const int32_t* layer_ids,
-                     int n_layers, const sse_pool_desc* d, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+static int embed_pooled(sse_model* m, const float* d_in, const int32_t* d_lengths, int B, int L,
+                        const int32_t* layer_ids, int n_layers, const sse_pool_desc* d, float* d_out, void* d_ws,
+                        size_t ws_bytes, void* stream, int ctx) {
   if (!m || !layer_ids || n_layers <= 0 || !d_out || !pool_desc_ok(d)) return SSE_ERR_INVALID;
   for (int i = 0; i < n_layers; ++i)
     if (layer_ids[i] < 0 || layer_ids[i] > m->cfg.layers) return SSE_ERR_INVALID;
   if (B <= 0 || L <= 0) return SSE_ERR_INVALID;
-  const int T = hs_frames(m, L);
+  const int T = hs_frames(m, L, ctx);
   if (T <= 0) return SSE_ERR_INVALID;
   Sink sk{layer_ids, n_layers, d_out, nullptr, B, T, m->cfg.hidden, (hipStream_t)stream};
   sk.m = m;
@@ -2041,7 +2096,26 @@ int sse_embed_pooled(sse_model* m, const float* d_in, const int32_t* d_lengths, 
   sk.nseg = pool_segments(T, d->win, d->hop);
   sk.nst = pool_nstats(d);
   // (a plain-mean description without valid-frame pooling takes the unchanged pool_mean launches: Sink::plain)
-  return forward(m, d_in, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream, false, nullptr, (const int*)d_lengths);
+  return forward(m, d_in, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream, false, nullptr, (const int*)d_lengths, ctx);
+}
+
+int sse_embed_pooled(sse_model* m, const float* d_in, const int32_t* d_lengths, int B, int L, const int32_t* layer_ids,
+                     int n_layers, const sse_pool_desc* d, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+  return embed_pooled(m, d_in, d_lengths, B, L, layer_ids, n_layers, d, d_out, d_ws, ws_bytes, stream, 0);
+}
+
+int sse_embed_pooled_ctx(sse_model* m, const float* d_in, const int32_t* d_lengths, int B, int L, int frames,
+                         const int32_t* layer_ids, int n_layers, const sse_pool_desc* d, float* d_out, void* d_ws,
+                         size_t ws_bytes, void* stream) {
+  if (!ctx_ok(m, frames)) return SSE_ERR_INVALID;
+  static const sse_pool_desc plain_mean = {SSE_STAT_MEAN, 0, 0, 0, 0};   // the time-mean of sse_embed / sse_embed_ragged
+  return embed_pooled(m, d_in, d_lengths, B, L, layer_ids, n_layers, d ? d : &plain_mean, d_out, d_ws, ws_bytes, stream,
+                      frames);
+}
+
+size_t sse_pool_out_floats_ctx(const sse_model* m, int B, int L, int frames, int n_layers, const sse_pool_desc* d) {
+  if (!ctx_ok(m, frames) || B <= 0 || L <= 0 || n_layers <= 0 || !pool_desc_ok(d)) return 0;
+  return (size_t)B * n_layers * pool_segments(frames, d->win, d->hop) * pool_nstats(d) * m->cfg.hidden;
 }
 
 int sse_pool(int dtype, const void* d_x, const int32_t* d_tlen, int B, int T, int H, const sse_pool_desc* d,
@@ -2066,6 +2140,13 @@ int sse_hidden_states(sse_model* m, const float* d_in, int B, int L, float* d_hs
   return forward(m, d_in, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+int sse_hidden_states_ctx(sse_model* m, const float* d_in, int B, int L, int frames, float* d_hs, void* d_ws,
+                          size_t ws_bytes, void* stream) {
+  if (!ctx_ok(m, frames) || !d_hs) return SSE_ERR_INVALID;
+  Sink sk{nullptr, 0, nullptr, d_hs, B, frames, m->cfg.hidden, (hipStream_t)stream};
+  return forward(m, d_in, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream, false, nullptr, nullptr, frames);
+}
+
 int sse_whisper_hidden_states_from_mel(sse_model* m, const float* d_mel, int B, float* d_hs, void* d_ws,
                                        size_t ws_bytes, void* stream) {
   if (!m || !d_hs || m->cfg.kind != SSE_KIND_WHISPER) return SSE_ERR_INVALID;
@@ -2073,9 +2154,16 @@ int sse_whisper_hidden_states_from_mel(sse_model* m, const float* d_mel, int B, 
   return forward(m, d_mel, B, 2 * m->cfg.max_positions, sk, d_ws, ws_bytes, (hipStream_t)stream, true);
 }
 
-int sse_whisper_embed(sse_model* m, const float* d_wave, int B, int L, const int32_t* enc_ids, int n_enc,
-                      float* d_enc_out, const int32_t* dec_ids, int n_dec, float* d_dec_out, void* d_ws,
-                      size_t ws_bytes, void* stream) {
+int sse_whisper_hidden_states_from_mel_ctx(sse_model* m, const float* d_mel, int B, int frames, float* d_hs,
+                                           void* d_ws, size_t ws_bytes, void* stream) {
+  if (!ctx_ok(m, frames) || !d_hs) return SSE_ERR_INVALID;
+  Sink sk{nullptr, 0, nullptr, d_hs, B, frames, m->cfg.hidden, (hipStream_t)stream};
+  return forward(m, d_mel, B, 2 * frames, sk, d_ws, ws_bytes, (hipStream_t)stream, true, nullptr, nullptr, frames);
+}
+
+static int whisper_embed(sse_model* m, const float* d_wave, int B, int L, const int32_t* enc_ids, int n_enc,
+                         float* d_enc_out, const int32_t* dec_ids, int n_dec, float* d_dec_out, void* d_ws,
+                         size_t ws_bytes, void* stream, int ctx) {
   if (!m || m->cfg.kind != SSE_KIND_WHISPER || n_enc < 0 || n_dec < 0 || (n_enc && (!enc_ids || !d_enc_out)) ||
       (n_dec && (!dec_ids || !d_dec_out)) || (n_dec && m->cfg.decoder_layers <= 0))
     return SSE_ERR_INVALID;
@@ -2083,36 +2171,62 @@ int sse_whisper_embed(sse_model* m, const float* d_wave, int B, int L, const int
     if (enc_ids[i] < 0 || enc_ids[i] > m->cfg.layers) return SSE_ERR_INVALID;
   for (int i = 0; i < n_dec; ++i)
     if (dec_ids[i] < 0 || dec_ids[i] > m->cfg.decoder_layers) return SSE_ERR_INVALID;
-  Sink sk{enc_ids, n_enc, d_enc_out, nullptr, B, m->cfg.max_positions, m->cfg.hidden, (hipStream_t)stream};
+  Sink sk{enc_ids, n_enc, d_enc_out, nullptr, B, whisper_ctx(m, ctx), m->cfg.hidden, (hipStream_t)stream};
   Sink dk{dec_ids, n_dec, d_dec_out, nullptr, B, 1, m->cfg.hidden, (hipStream_t)stream};
-  return forward(m, d_wave, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream, false, n_dec ? &dk : nullptr);
+  return forward(m, d_wave, B, L, sk, d_ws, ws_bytes, (hipStream_t)stream, false, n_dec ? &dk : nullptr, nullptr, ctx);
 }
 
-int sse_whisper_decoder_hidden_states(sse_model* m, const float* d_enc, int B, float* d_hs, void* d_ws,
-                                      size_t ws_bytes, void* stream) {
+int sse_whisper_embed(sse_model* m, const float* d_wave, int B, int L, const int32_t* enc_ids, int n_enc,
+                      float* d_enc_out, const int32_t* dec_ids, int n_dec, float* d_dec_out, void* d_ws,
+                      size_t ws_bytes, void* stream) {
+  return whisper_embed(m, d_wave, B, L, enc_ids, n_enc, d_enc_out, dec_ids, n_dec, d_dec_out, d_ws, ws_bytes, stream, 0);
+}
+
+int sse_whisper_embed_ctx(sse_model* m, const float* d_wave, int B, int L, int frames, const int32_t* enc_ids,
+                          int n_enc, float* d_enc_out, const int32_t* dec_ids, int n_dec, float* d_dec_out,
+                          void* d_ws, size_t ws_bytes, void* stream) {
+  if (!ctx_ok(m, frames)) return SSE_ERR_INVALID;
+  return whisper_embed(m, d_wave, B, L, enc_ids, n_enc, d_enc_out, dec_ids, n_dec, d_dec_out, d_ws, ws_bytes, stream,
+                       frames);
+}
+
+static int whisper_decoder_hs(sse_model* m, const float* d_enc, int B, int Tq, float* d_hs, void* d_ws, size_t ws_bytes,
+                              void* stream) {
   if (!m || !d_enc || !d_hs || B <= 0 || m->cfg.kind != SSE_KIND_WHISPER || m->cfg.decoder_layers <= 0)
     return SSE_ERR_INVALID;
-  if (ws_bytes < sse_workspace_bytes(m, B, 2 * m->cfg.max_positions)) return SSE_ERR_WORKSPACE;
+  if (ws_bytes < workspace_bytes(m, B, 2 * Tq, Tq)) return SSE_ERR_WORKSPACE;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return SSE_ERR_HIP;
   if (dev != m->device && hipSetDevice(m->device) != hipSuccess) return SSE_ERR_HIP;
   hipStream_t s = (hipStream_t)stream;
   Plan p;
-  const WhisperWs w = whisper_plan(m, B, p);
+  const WhisperWs w = whisper_plan(m, B, Tq, p);
   char* ws = (char*)d_ws;
   Sink dk{nullptr, 0, nullptr, d_hs, B, 1, m->cfg.hidden, s};
-  const long long n = (long long)B * m->cfg.max_positions * m->cfg.hidden;
+  const long long n = (long long)B * Tq * m->cfg.hidden;
   int rc = hipMemsetAsync(ws + w.zero, 0, 256, s) == hipSuccess ? 0 : SSE_ERR_HIP;
   if (!rc) {
     if (m->bf()) {
       rc = launch_cast<bf16>(d_enc, n, (bf16*)(ws + w.xb), s);
-      if (!rc) rc = whisper_decoder<bf16>(m, (const bf16*)(ws + w.xb), B, dk, ws, w, s);
+      if (!rc) rc = whisper_decoder<bf16>(m, (const bf16*)(ws + w.xb), B, Tq, dk, ws, w, s);
     } else {
-      rc = whisper_decoder<float>(m, d_enc, B, dk, ws, w, s);
+      rc = whisper_decoder<float>(m, d_enc, B, Tq, dk, ws, w, s);
     }
   }
   if (dev != m->device) (void)hipSetDevice(dev);
   return rc;
+}
+
+int sse_whisper_decoder_hidden_states(sse_model* m, const float* d_enc, int B, float* d_hs, void* d_ws,
+                                      size_t ws_bytes, void* stream) {
+  if (!m) return SSE_ERR_INVALID;
+  return whisper_decoder_hs(m, d_enc, B, m->cfg.max_positions, d_hs, d_ws, ws_bytes, stream);
+}
+
+int sse_whisper_decoder_hidden_states_ctx(sse_model* m, const float* d_enc, int B, int frames, float* d_hs, void* d_ws,
+                                          size_t ws_bytes, void* stream) {
+  if (!ctx_ok(m, frames)) return SSE_ERR_INVALID;
+  return whisper_decoder_hs(m, d_enc, B, frames, d_hs, d_ws, ws_bytes, stream);
 }
 
 int sse_profile_start(sse_model* m, int max_launches) {

@@ -22,6 +22,7 @@ import struct
 import numpy as np
 import torch
 
+from . import config as C
 from ._lib import SSEOutOfMemoryError
 from .hf import WavLMModel, WhisperModel
 from .model import POOL_STATS, pool_mask
@@ -175,14 +176,20 @@ def extract_wavlm_embeddings(audio_file, model, feature_extractor, device, layer
 
 
 def extract_embeddings_from_audio_whisper(audio_array, model, processor, device, layer_names, *, pooling="mean",
-                                          window=None, valid_only=False):
+                                          window=None, valid_only=False, frames=None):
     """REF/model_training_1.py:268-316 (in-memory twin): ``encoder_layer_<i>`` time-means and
     ``decoder_layer_<i>`` states of the 1-token decoder pass, in ``layer_names`` order.  A model
     built without the decoder (decoder_layers=0) reports and skips decoder names.  ``pooling`` (keyword-only)
     selects the statistics of the encoder vectors (float32[n_stats*H]; the 1-token decoder states stay [H]);
-    ``valid_only`` pools the encoder frames that cover the clip instead of the 30 s pad."""
+    ``valid_only`` pools the encoder frames that cover the clip instead of the 30 s pad.  ``frames`` (HIP
+    ``WhisperModel`` only; ValueError with any other model): the audio context of SSEModel.embed, an int or
+    "clip" -- the encoder runs that many frames instead of 1500, a different feature from the reference's."""
     _no_window(window)
     pool_mask(pooling)
+    if frames is not None:
+        if not isinstance(model, WhisperModel):
+            raise ValueError("frames= (the Whisper audio context) needs the HIP WhisperModel")
+        C.resolve_frames(model.sse.spec, frames, int(np.asarray(audio_array).shape[-1]))
     try:
         wanted = []
         for n in layer_names:
@@ -199,7 +206,8 @@ def extract_embeddings_from_audio_whisper(audio_array, model, processor, device,
                 if not enc and not dec:
                     return {}
                 wave = torch.from_numpy(np.ascontiguousarray(np.asarray(audio_array, np.float32)))
-                e, dd = model.sse.whisper_embed(wave.to(model.sse.device), enc, dec, pool=pooling, valid_only=valid_only)
+                e, dd = model.sse.whisper_embed(wave.to(model.sse.device), enc, dec, pool=pooling, valid_only=valid_only,
+                                                frames=frames)
                 e, dd = e.cpu().numpy(), dd.cpu().numpy()
                 out = {}
                 for d, i, n in wanted:
@@ -237,9 +245,9 @@ def extract_embeddings_from_audio_whisper(audio_array, model, processor, device,
 
 
 def extract_whisper_embeddings_fixed(audio_file, model, processor, device, encoder_indices, decoder_indices, *,
-                                     pooling="mean", window=None, valid_only=False):
+                                     pooling="mean", window=None, valid_only=False, frames=None):
     """REF/whisper_embeddings_large.py:234-299: encoder time-means + 1-token decoder states.
-    ``pooling`` / ``valid_only``: as extract_embeddings_from_audio_whisper."""
+    ``pooling`` / ``valid_only`` / ``frames``: as extract_embeddings_from_audio_whisper."""
     _no_window(window)
     pool_mask(pooling)
     audio = load_audio(audio_file, device=device)
@@ -254,4 +262,4 @@ def extract_whisper_embeddings_fixed(audio_file, model, processor, device, encod
                 logger.warning(f"Decoder layer {i} is out of range (max: {model.sse.spec.decoder_layers})")
     names = [f"encoder_layer_{i}" for i in encoder_indices] + [f"decoder_layer_{i}" for i in decoder_indices]
     return extract_embeddings_from_audio_whisper(audio, model, processor, device, names, pooling=pooling,
-                                                 valid_only=valid_only)
+                                                 valid_only=valid_only, frames=frames)

@@ -93,10 +93,13 @@ class WhisperFeatureExtractor:
         self.sampling_rate = sampling_rate
         self.device = torch.device(device)
 
-    def __call__(self, raw_speech, sampling_rate=None, return_tensors="pt", **_):
+    def __call__(self, raw_speech, sampling_rate=None, return_tensors="pt", frames=None, **_):
+        """``frames`` (no HF counterpart): the audio context F of SSEModel.embed -> input_features [B, n_mels, 2F],
+        which the encoder twin runs at that context."""
         if sampling_rate is not None and sampling_rate != self.sampling_rate:
             raise ValueError(f"expected sampling_rate={self.sampling_rate}, got {sampling_rate}")
-        return BatchFeature(input_features=logmel(_to_batch(raw_speech, self.device), self.feature_size))
+        return BatchFeature(input_features=logmel(_to_batch(raw_speech, self.device), self.feature_size,
+                                                  frames=frames))
 
 
 WhisperProcessor = WhisperFeatureExtractor
@@ -173,11 +176,12 @@ class _DuckModel:
     def eval(self):
         return self
 
-    def embed(self, wave, layer_indices, *, pooling="mean", window=None, hop=None, ddof=1, valid_only=False):
+    def embed(self, wave, layer_indices, *, pooling="mean", window=None, hop=None, ddof=1, valid_only=False,
+              frames=None):
         """SSEModel.embed; ``pooling`` and the other keyword-only arguments are its pool / window / hop / ddof /
-        valid_only (the defaults are the reference's time-mean)."""
+        valid_only / frames (the defaults are the reference's time-mean over the reference's frames)."""
         return self.sse.embed(wave, layer_indices, pool=pooling, window=window, hop=hop, ddof=ddof,
-                              valid_only=valid_only)
+                              valid_only=valid_only, frames=frames)
 
 
 class WavLMModel(_DuckModel):
@@ -206,6 +210,8 @@ class _WhisperEncoder:
         self.sse = sse
 
     def __call__(self, input_features, attention_mask=None, output_hidden_states=None, return_dict=True, **_):
+        # input_features [B, n_mels, 2F]: 3000 wide as HF's, or narrower = the audio context F (HF's own encoder
+        # rejects those; SSEModel.hidden_states_from_mel runs embed_positions[:F])
         hs = self.sse.hidden_states_from_mel(input_features.to(self.sse.device))
         return BaseModelOutput(last_hidden_state=hs[-1], hidden_states=hs if output_hidden_states else None)
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import WavLMSpec, WhisperSpec, param_specs
+from .config import WavLMSpec, WhisperSpec, param_specs, resolve_frames
 
 DTYPES = {"fp32": _lib.SSE_DTYPE_F32, "float32": _lib.SSE_DTYPE_F32, "f32": _lib.SSE_DTYPE_F32,
           "bf16": _lib.SSE_DTYPE_BF16, "bfloat16": _lib.SSE_DTYPE_BF16,
@@ -153,13 +153,22 @@ class SSEModel:
     def hidden_size(self) -> int:
         return self.spec.hidden
 
-    def output_frames(self, n_samples: int) -> int:
-        return _lib.lib().sse_output_frames(self._h, int(n_samples))
+    def output_frames(self, n_samples: int, *, frames=None) -> int:
+        F = resolve_frames(self.spec, frames, n_samples)
+        return F if F is not None else _lib.lib().sse_output_frames(self._h, int(n_samples))
 
-    def workspace(self, B: int, L: int) -> torch.Tensor:
-        n = _lib.lib().sse_workspace_bytes(self._h, int(B), int(L))
+    def workspace_bytes(self, B: int, L: int, *, frames=None) -> int:
+        """Device workspace a call on B clips of L samples needs; ``frames`` (Whisper audio context): every
+        B * T term scales with it."""
+        F = resolve_frames(self.spec, frames, L)
+        if F is None:
+            return int(_lib.lib().sse_workspace_bytes(self._h, int(B), int(L)))
+        return int(_lib.lib().sse_workspace_bytes_ctx(self._h, int(B), int(L), F))
+
+    def workspace(self, B: int, L: int, *, frames=None) -> torch.Tensor:
+        n = self.workspace_bytes(B, L, frames=frames)
         if n == 0:
-            raise _lib.SSEError(-1, f"sse_workspace_bytes(B={B}, L={L})")
+            raise _lib.SSEError(-1, f"sse_workspace_bytes(B={B}, L={L}, frames={frames})")
         if self._ws is None or self._ws.numel() < n:
             self._ws = None
             self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
@@ -209,10 +218,11 @@ class SSEModel:
         _lib.check(_lib.lib().sse_profile_stop(self._h), "sse_profile_stop")
 
     # -- compute --------------------------------------------------------------------------
-    def pool_segments(self, n_samples: int, window=None, hop=None, valid_only: bool = False) -> int:
-        """Segments embed(window=, hop=) fills for a clip of n_samples (the rest of its slots are zeros)."""
+    def pool_segments(self, n_samples: int, window=None, hop=None, valid_only: bool = False, *, frames=None) -> int:
+        """Segments embed(window=, hop=) fills for a clip of n_samples (the rest of its slots are zeros);
+        ``frames``: the Whisper audio context of that embed call."""
         d = pool_desc("mean", window, hop, 1, valid_only)
-        T = self.output_frames(n_samples)
+        T = self.output_frames(n_samples, frames=frames)
         if d.valid_only and isinstance(self.spec, WhisperSpec):
             T = min(T, -(-int(n_samples) // 320))
         if T <= 0:
@@ -221,7 +231,8 @@ class SSEModel:
 
     def embed(self, wave: torch.Tensor, layer_indices, out: torch.Tensor | None = None,
               lengths=None, workspace: torch.Tensor | None = None, check_range: bool | None = None, *,
-              pool="mean", window=None, hop=None, ddof: int = 1, valid_only: bool = False) -> torch.Tensor:
+              pool="mean", window=None, hop=None, ddof: int = 1, valid_only: bool = False,
+              frames=None) -> torch.Tensor:
         """[B, L] fp32 16 kHz waves -> [B, len(layer_indices), H] fp32 time-means of hidden states.
         ``lengths`` (ragged batch): samples of each clip, its first lengths[b] samples of row b; each
         clip is embedded at its own length (sse_embed_ragged).  ``check_range`` overrides the model's
@@ -233,10 +244,17 @@ class SSEModel:
         (frames, window % hop == 0) pool windows instead of the clip -> [B, n_layers, S, n_stats*H];
         a shorter clip of a ragged batch fills its first ``pool_segments(n_samples, window, hop)`` slots, the
         rest are zeros.  ``valid_only`` (Whisper): pool the ceil(n_samples / 320) frames that cover the clip,
-        not the 30 s pad.  With all of these at their defaults the call is the plain time-mean above."""
+        not the 30 s pad.  With all of these at their defaults the call is the plain time-mean above.
+
+        ``frames`` (Whisper audio context, DESIGN.md §3): None = the reference's 1500 encoder frames (30 s);
+        an int F in [1, 1500] encodes only the first F frames (320 samples each) of every clip -- log-mel,
+        convolutions, attention keys and pooling all stop at F; "clip" = the smallest context that covers the
+        batch, ``spec.context_frames(L)`` or that of the longest of ``lengths``.  Embeddings at different
+        contexts are different features: use one context for training and test."""
         desc = pool_desc(pool, window, hop, ddof, valid_only)
-        if not (desc.stats == _lib.SSE_STAT_MEAN and desc.win == 0 and not desc.valid_only):
-            return self._embed_pooled(wave, layer_indices, out, lengths, workspace, check_range, desc)
+        F = resolve_frames(self.spec, frames, wave.shape[-1] if isinstance(wave, torch.Tensor) else 0, lengths)
+        if F is not None or not (desc.stats == _lib.SSE_STAT_MEAN and desc.win == 0 and not desc.valid_only):
+            return self._embed_pooled(wave, layer_indices, out, lengths, workspace, check_range, desc, F)
         wave = self._check_wave(wave)
         B, L = wave.shape
         ids = torch.tensor([int(i) for i in layer_indices], dtype=torch.int32)
@@ -269,12 +287,12 @@ class SSEModel:
         self._after(check_range)
         return out
 
-    def _embed_pooled(self, wave, layer_indices, out, lengths, workspace, check_range, desc) -> torch.Tensor:
+    def _embed_pooled(self, wave, layer_indices, out, lengths, workspace, check_range, desc, F=None) -> torch.Tensor:
         wave = self._check_wave(wave)
         B, L = wave.shape
         ids = torch.tensor([int(i) for i in layer_indices], dtype=torch.int32)
         n = ids.numel()
-        T = self.output_frames(L)
+        T = self.output_frames(L, frames=F)
         if T <= 0:
             raise _lib.SSEError(-1, "a clip is shorter than the conv receptive field")
         S = int(_lib.lib().sse_pool_segments(T, desc.win, desc.hop))
@@ -285,9 +303,12 @@ class SSEModel:
         elif (out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != shape
               or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous fp32 {list(shape)} tensor on {self.device}")
-        assert out.numel() == _lib.lib().sse_pool_out_floats(self._h, B, L, n, ctypes.byref(desc))
-        ws = self.workspace(B, L) if workspace is None else workspace
-        if ws.numel() < _lib.lib().sse_workspace_bytes(self._h, int(B), int(L)):
+        if F is None:
+            assert out.numel() == _lib.lib().sse_pool_out_floats(self._h, B, L, n, ctypes.byref(desc))
+        else:
+            assert out.numel() == _lib.lib().sse_pool_out_floats_ctx(self._h, B, L, F, n, ctypes.byref(desc))
+        ws = self.workspace(B, L, frames=F) if workspace is None else workspace
+        if ws.numel() < self.workspace_bytes(B, L, frames=F):
             raise ValueError("workspace too small")
         d_len = None
         if lengths is not None:
@@ -297,16 +318,23 @@ class SSEModel:
             if isinstance(self.spec, WavLMSpec) and min(self.spec.frames(v) for v in lens) <= 0:
                 raise _lib.SSEError(-1, "a clip is shorter than the conv receptive field")
             d_len = torch.tensor(lens, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
-        _lib.check(_lib.lib().sse_embed_pooled(self._h, wave.data_ptr(), d_len.data_ptr() if d_len is not None else None,
-                                               B, L, ids.data_ptr(), n, ctypes.byref(desc), out.data_ptr(),
-                                               ws.data_ptr(), ws.numel(), self._stream()), "sse_embed_pooled")
+        d_len_p = d_len.data_ptr() if d_len is not None else None
+        if F is None:
+            _lib.check(_lib.lib().sse_embed_pooled(self._h, wave.data_ptr(), d_len_p, B, L, ids.data_ptr(), n,
+                                                   ctypes.byref(desc), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   self._stream()), "sse_embed_pooled")
+        else:
+            _lib.check(_lib.lib().sse_embed_pooled_ctx(self._h, wave.data_ptr(), d_len_p, B, L, F, ids.data_ptr(), n,
+                                                       ctypes.byref(desc), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       self._stream()), "sse_embed_pooled_ctx")
         self._after(check_range)
         return out
 
     def embed_clips(self, clips, layer_indices, **pooling) -> torch.Tensor:
         """A list of 1-D clips of any lengths -> [N, len(layer_indices), H]: one ragged batch
         (zero-padded rows + lengths), every clip embedded at its own length.  ``pooling``: the
-        pool / window / hop / ddof / valid_only arguments of ``embed``."""
+        pool / window / hop / ddof / valid_only / frames arguments of ``embed`` (frames="clip": the context
+        of the longest clip, shared by the batch)."""
         lens = [int(c.shape[-1]) for c in clips]
         wave = torch.zeros((len(clips), max(lens)), dtype=torch.float32, device=self.device)
         for i, c in enumerate(clips):
@@ -314,57 +342,74 @@ class SSEModel:
             wave[i, :lens[i]] = c.to(self.device, torch.float32)
         return self.embed(wave, layer_indices, lengths=lens, **pooling)
 
-    def hidden_states(self, wave: torch.Tensor) -> tuple:
-        """[B, L] -> tuple of layers+1 tensors [B, T, H] (HF ``output_hidden_states`` semantics)."""
+    def hidden_states(self, wave: torch.Tensor, *, frames=None) -> tuple:
+        """[B, L] -> tuple of layers+1 tensors [B, T, H] (HF ``output_hidden_states`` semantics).
+        ``frames`` (Whisper audio context, see ``embed``): T = F instead of 1500."""
+        F = resolve_frames(self.spec, frames, wave.shape[-1] if isinstance(wave, torch.Tensor) else 0)
         wave = self._check_wave(wave)
         B, L = wave.shape
-        T = self.output_frames(L)
+        T = self.output_frames(L, frames=F)
         n_hs = self.spec.layers + 1
         hs = torch.empty((n_hs, B, T, self.spec.hidden), dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, L)
-        _lib.check(_lib.lib().sse_hidden_states(self._h, wave.data_ptr(), B, L, hs.data_ptr(), ws.data_ptr(),
-                                                ws.numel(), self._stream()), "sse_hidden_states")
+        ws = self.workspace(B, L, frames=F)
+        if F is None:
+            _lib.check(_lib.lib().sse_hidden_states(self._h, wave.data_ptr(), B, L, hs.data_ptr(), ws.data_ptr(),
+                                                    ws.numel(), self._stream()), "sse_hidden_states")
+        else:
+            _lib.check(_lib.lib().sse_hidden_states_ctx(self._h, wave.data_ptr(), B, L, F, hs.data_ptr(), ws.data_ptr(),
+                                                        ws.numel(), self._stream()), "sse_hidden_states_ctx")
         self._after()
         return tuple(hs.unbind(0))
 
     def hidden_states_from_mel(self, mel: torch.Tensor) -> tuple:
-        """Whisper only: [B, n_mels, 3000] log-mel -> layers+1 tensors [B, 1500, H]."""
+        """Whisper only: [B, n_mels, 3000] log-mel -> layers+1 tensors [B, 1500, H]; a log-mel of width 2F
+        (``logmel(frames=F)``, or HF input_features[:, :, :2F]) runs the audio context F -> [B, F, H]."""
         if not isinstance(self.spec, WhisperSpec):
             raise TypeError("hidden_states_from_mel is Whisper-only")
         if mel.device != self.device:
             raise ValueError(f"expected a tensor on {self.device}")
         mel = mel.to(torch.float32).contiguous()
-        if mel.dim() != 3 or mel.shape[1] != self.spec.n_mels or mel.shape[2] != 2 * self.spec.max_positions:
-            raise ValueError(f"expected [B, {self.spec.n_mels}, {2 * self.spec.max_positions}] log-mel, "
-                             f"got {tuple(mel.shape)}")
+        W = mel.shape[2] if mel.dim() == 3 else 0
+        if mel.dim() != 3 or mel.shape[1] != self.spec.n_mels or W % 2 or not 2 <= W <= 2 * self.spec.max_positions:
+            raise ValueError(f"expected [B, {self.spec.n_mels}, 2F] log-mel with F in [1, {self.spec.max_positions}] "
+                             f"({2 * self.spec.max_positions} wide without an audio context), got {tuple(mel.shape)}")
         B = mel.shape[0]
-        T = self.spec.max_positions
+        T = W // 2
         hs = torch.empty((self.spec.layers + 1, B, T, self.spec.hidden), dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, self.spec.n_samples)
-        _lib.check(_lib.lib().sse_whisper_hidden_states_from_mel(self._h, mel.data_ptr(), B, hs.data_ptr(),
-                                                                 ws.data_ptr(), ws.numel(), self._stream()),
-                   "sse_whisper_hidden_states_from_mel")
+        if T == self.spec.max_positions:
+            ws = self.workspace(B, self.spec.n_samples)
+            _lib.check(_lib.lib().sse_whisper_hidden_states_from_mel(self._h, mel.data_ptr(), B, hs.data_ptr(),
+                                                                     ws.data_ptr(), ws.numel(), self._stream()),
+                       "sse_whisper_hidden_states_from_mel")
+        else:
+            ws = self.workspace(B, self.spec.n_samples, frames=T)
+            _lib.check(_lib.lib().sse_whisper_hidden_states_from_mel_ctx(self._h, mel.data_ptr(), B, T, hs.data_ptr(),
+                                                                         ws.data_ptr(), ws.numel(), self._stream()),
+                       "sse_whisper_hidden_states_from_mel_ctx")
         return tuple(hs.unbind(0))
 
 
     def whisper_embed(self, wave: torch.Tensor, encoder_indices, decoder_indices, enc_out=None, dec_out=None, *,
-                      pool="mean", window=None, hop=None, ddof: int = 1, valid_only: bool = False):
+                      pool="mean", window=None, hop=None, ddof: int = 1, valid_only: bool = False, frames=None):
         """Whisper: encoder time-means AND 1-token decoder states in one pass
         (REF/whisper_embeddings_large.py:234-299) -> ([B, n_enc, H], [B, n_dec, H]) fp32.
         The pooling arguments (``embed``) apply to the encoder output only (the decoder has one token);
-        a non-default pooling runs the encoder statistics and the decoder states as two calls."""
+        a non-default pooling runs the encoder statistics and the decoder states as two calls.
+        ``frames`` (audio context, see ``embed``): the encoder runs F frames and the decoder cross-attends
+        over those F."""
         if not isinstance(self.spec, WhisperSpec):
             raise TypeError("whisper_embed is Whisper-only")
+        F = resolve_frames(self.spec, frames, wave.shape[-1] if isinstance(wave, torch.Tensor) else 0)
         if decoder_indices and not self.spec.decoder_layers:
             raise ValueError(f"{self.spec.name} was built without the decoder (decoder_layers=0)")
         desc = pool_desc(pool, window, hop, ddof, valid_only)
         if not (desc.stats == _lib.SSE_STAT_MEAN and desc.win == 0 and not desc.valid_only):
             if len(encoder_indices):
-                enc_out = self._embed_pooled(wave, encoder_indices, enc_out, None, None, None, desc)
+                enc_out = self._embed_pooled(wave, encoder_indices, enc_out, None, None, None, desc, F)
             else:
                 enc_out = torch.empty((self._check_wave(wave).shape[0], 0, _n_stats(desc) * self.spec.hidden),
                                       dtype=torch.float32, device=self.device)
-            _, dec_out = self.whisper_embed(wave, [], decoder_indices, None, dec_out)
+            _, dec_out = self.whisper_embed(wave, [], decoder_indices, None, dec_out, frames=F)
             return enc_out, dec_out
         wave = self._check_wave(wave)
         B, L = wave.shape
@@ -375,43 +420,69 @@ class SSEModel:
             enc_out = torch.empty((B, eid.numel(), H), dtype=torch.float32, device=self.device)
         if dec_out is None:
             dec_out = torch.empty((B, did.numel(), H), dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, L)
-        _lib.check(_lib.lib().sse_whisper_embed(self._h, wave.data_ptr(), B, L, eid.data_ptr(), eid.numel(),
-                                                enc_out.data_ptr() if eid.numel() else None, did.data_ptr(),
-                                                did.numel(), dec_out.data_ptr() if did.numel() else None,
-                                                ws.data_ptr(), ws.numel(), self._stream()), "sse_whisper_embed")
+        ws = self.workspace(B, L, frames=F)
+        outs = (eid.data_ptr(), eid.numel(), enc_out.data_ptr() if eid.numel() else None, did.data_ptr(), did.numel(),
+                dec_out.data_ptr() if did.numel() else None, ws.data_ptr(), ws.numel(), self._stream())
+        if F is None:
+            _lib.check(_lib.lib().sse_whisper_embed(self._h, wave.data_ptr(), B, L, *outs), "sse_whisper_embed")
+        else:
+            _lib.check(_lib.lib().sse_whisper_embed_ctx(self._h, wave.data_ptr(), B, L, F, *outs),
+                       "sse_whisper_embed_ctx")
         return enc_out, dec_out
 
     def decoder_hidden_states(self, enc: torch.Tensor) -> tuple:
         """Whisper: ``model.decoder(input_ids=zeros([B, 1]), encoder_hidden_states=enc)`` hidden states:
-        enc [B, 1500, H] -> decoder_layers+1 tensors [B, 1, H] fp32."""
+        enc [B, 1500, H] -> decoder_layers+1 tensors [B, 1, H] fp32; enc [B, F, H] (the last state of an
+        audio context F) cross-attends over those F frames."""
         if not isinstance(self.spec, WhisperSpec) or not self.spec.decoder_layers:
             raise TypeError("decoder_hidden_states needs a Whisper spec with decoder_layers > 0")
-        T, H = self.spec.max_positions, self.spec.hidden
-        if enc.device != self.device or enc.dim() != 3 or tuple(enc.shape[1:]) != (T, H):
-            raise ValueError(f"expected [B, {T}, {H}] encoder states on {self.device}, got {tuple(enc.shape)}")
+        H = self.spec.hidden
+        if (enc.device != self.device or enc.dim() != 3 or enc.shape[2] != H
+                or not 1 <= enc.shape[1] <= self.spec.max_positions):
+            raise ValueError(f"expected [B, F <= {self.spec.max_positions}, {H}] encoder states on {self.device}, "
+                             f"got {tuple(enc.shape)}")
+        T = enc.shape[1]
         enc = enc.to(torch.float32).contiguous()
         B = enc.shape[0]
         hs = torch.empty((self.spec.decoder_layers + 1, B, 1, H), dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, self.spec.n_samples)
-        _lib.check(_lib.lib().sse_whisper_decoder_hidden_states(self._h, enc.data_ptr(), B, hs.data_ptr(),
-                                                                ws.data_ptr(), ws.numel(), self._stream()),
-                   "sse_whisper_decoder_hidden_states")
+        if T == self.spec.max_positions:
+            ws = self.workspace(B, self.spec.n_samples)
+            _lib.check(_lib.lib().sse_whisper_decoder_hidden_states(self._h, enc.data_ptr(), B, hs.data_ptr(),
+                                                                    ws.data_ptr(), ws.numel(), self._stream()),
+                       "sse_whisper_decoder_hidden_states")
+        else:
+            ws = self.workspace(B, self.spec.n_samples, frames=T)
+            _lib.check(_lib.lib().sse_whisper_decoder_hidden_states_ctx(self._h, enc.data_ptr(), B, T, hs.data_ptr(),
+                                                                        ws.data_ptr(), ws.numel(), self._stream()),
+                       "sse_whisper_decoder_hidden_states_ctx")
         return tuple(hs.unbind(0))
 
 
-def logmel(wave: torch.Tensor, n_mels: int = 80) -> torch.Tensor:
-    """Whisper log-mel on device: [B, L] (L <= 480000) -> [B, n_mels, 3000] (HF layout)."""
+_LOGMEL_SPEC = WhisperSpec()   # the log-mel's frame arithmetic is the same for every Whisper (1500 frames of 320)
+
+
+def logmel(wave: torch.Tensor, n_mels: int = 80, *, frames=None) -> torch.Tensor:
+    """Whisper log-mel on device: [B, L] (L <= 480000) -> [B, n_mels, 3000] (HF layout).  ``frames`` (audio
+    context F, an int or "clip"): the log-mel of each clip cut at 320 F samples, mel frames [0, 2F) ->
+    [B, n_mels, 2F], the per-clip max of the -8 clamp over those frames."""
+    F = resolve_frames(_LOGMEL_SPEC, frames, wave.shape[-1])
     if wave.dim() == 1:
         wave = wave[None]
     wave = wave.to(torch.float32).contiguous()
     B, L = wave.shape
     L_ = _lib.lib()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(wave.device).cuda_stream)
+    if F is not None:
+        n = L_.sse_logmel_workspace_bytes_ctx(B, n_mels, F)
+        ws = torch.empty(n, dtype=torch.uint8, device=wave.device)
+        out = torch.empty((B, n_mels, 2 * F), dtype=torch.float32, device=wave.device)
+        _lib.check(L_.sse_logmel_ctx(wave.data_ptr(), B, L, n_mels, F, out.data_ptr(), ws.data_ptr(), n, stream),
+                   "sse_logmel_ctx")
+        return out
     n = L_.sse_logmel_workspace_bytes(B, n_mels)
     ws = torch.empty(n, dtype=torch.uint8, device=wave.device)
     out = torch.empty((B, n_mels, 3000), dtype=torch.float32, device=wave.device)
-    _lib.check(L_.sse_logmel(wave.data_ptr(), B, L, n_mels, out.data_ptr(), ws.data_ptr(), n,
-                             ctypes.c_void_p(torch.cuda.current_stream(wave.device).cuda_stream)), "sse_logmel")
+    _lib.check(L_.sse_logmel(wave.data_ptr(), B, L, n_mels, out.data_ptr(), ws.data_ptr(), n, stream), "sse_logmel")
     return out
 
 
