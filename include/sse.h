@@ -34,8 +34,20 @@ extern "C" {
 #endif
 
 enum sse_kind { SSE_KIND_WAVLM = 0, SSE_KIND_WHISPER = 1 };
-/* SSE_DTYPE_FP8 (Whisper): bf16 activations, the encoder layers' QKV / fc1 / fc2 GEMMs in MX-fp8
- * (OCP e4m3 operands, one E8M0 scale per 32 K-elements, BASELINE configs[4] "fp8 MFMA encoder"). */
+/* SSE_DTYPE_FP8 (Whisper; WavLM with the stable-LN encoder): bf16 activations, the encoder layers' QKV / fc1 /
+ * fc2 GEMMs in MX-fp8 (OCP e4m3 operands, one E8M0 scale per 32 K-elements, BASELINE configs[4] "fp8 MFMA
+ * encoder").
+ * WavLM: accepted for stable_layer_norm == 1 with hidden % 256 == 0, ffn % 256 == 0 and hidden <= 2048
+ * (WavLM-large).  In MX-fp8: each layer's packed QKV GEMM (q | k | v | the gate rows of gru_rel_pos_linear | pad),
+ * fc1 (GELU, MX-fp8 out) and fc2 (the bf16 residual stream in place), their A operands written by the two
+ * LayerNorms.  In bf16 as in SSE_DTYPE_BF16: the conv front end, feature projection, positional conv, the gated
+ * relative-position attention, the out-projection, the residual stream and the pooling.  Same entry points,
+ * ragged batches, pooling and hidden states as the other dtypes; sse_weight_floats is unchanged.  Measured on
+ * MI355X: 0.0586 rel-L2 / 0.99828 cosine against the reference's WavLM-large fixture (bf16: 0.006; the
+ * bar is 0.08 / 0.995), 11.2k against 8.7k clips/s for bf16 (256 x 3 s, one box) -- an opt-in mode.
+ * Post-LN WavLM (stable_layer_norm == 0, WavLM-base) is refused with SSE_ERR_UNSUPPORTED: its LayerNorms
+ * re-normalise the quantisation error into the stream at every sub-layer, and the format alone costs 0.093
+ * rel-L2 against the fp8 bar of 0.08 (emulated; DESIGN.md §3 "MX-fp8 for stable-LN WavLM"). */
 /* SSE_DTYPE_FP16X3 (WavLM with the "group" frontend and post-LN encoder, i.e. WavLM-base): the
  * fp32 path with every dense GEMM / strided conv on the fp16 matrix cores in split form: operands
  * x = hi + lo (two fp16, the lo plane carried scaled by 2^11 and the weights by a power of two so no

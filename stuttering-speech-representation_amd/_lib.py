@@ -18,11 +18,12 @@ LIB_PATH = os.path.join(_HERE, "libsse.so")
 
 SSE_DTYPE_F32 = 0
 SSE_DTYPE_BF16 = 1
-SSE_DTYPE_FP8 = 2   # bf16 activations + MX-fp8 encoder-layer GEMMs (Whisper)
+SSE_DTYPE_FP8 = 2   # bf16 activations + MX-fp8 encoder-layer GEMMs (Whisper, stable-LN WavLM; not post-LN WavLM)
 SSE_DTYPE_FP16X3 = 3   # fp32 activations, split-fp16 (hi/lo) GEMMs: fp32-class results (WavLM-base)
 SSE_DTYPE_FP16 = 4   # the bf16 path with fp16 activations / weights / MFMA operands (WavLM-base)
 SSE_STAT_MEAN, SSE_STAT_STD, SSE_STAT_MAX = 1, 2, 4   # sse_pool_desc.stats bits (output order: mean, std, max)
 SSE_ERR_INVALID = -1
+SSE_ERR_UNSUPPORTED = -3
 SSE_ERR_WORKSPACE = -4
 SSE_ERR_OOM = -6
 SSE_ERR_RANGE = -7   # an fp16-range call wrote a non-finite value (sse_check_range)

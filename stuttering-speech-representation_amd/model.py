@@ -22,6 +22,7 @@ DTYPES = {"fp32": _lib.SSE_DTYPE_F32, "float32": _lib.SSE_DTYPE_F32, "f32": _lib
           "bf16": _lib.SSE_DTYPE_BF16, "bfloat16": _lib.SSE_DTYPE_BF16,
           "fp8": _lib.SSE_DTYPE_FP8, "mxfp8": _lib.SSE_DTYPE_FP8, "fp16x3": _lib.SSE_DTYPE_FP16X3,
           "fp16": _lib.SSE_DTYPE_FP16, "float16": _lib.SSE_DTYPE_FP16}
+# fp8 / mxfp8: Whisper and stable-LN WavLM (WavLM-large); post-LN WavLM (WavLM-base) raises, see SSEModel
 # dtypes whose activations live in the fp16 range: their calls are range-checked (sse_check_range)
 FP16_RANGE = ("fp16", "float16", "fp16x3")
 
@@ -103,9 +104,10 @@ def pack_weights(spec, state_dict: dict) -> np.ndarray:
 class SSEModel:
     """One model on one GPU.  ``dtype``: "bf16" (throughput path), "fp32" (parity path), "fp16x3"
     (WavLM-base: fp32 activations, split-fp16 GEMMs -- fp32-class parity at ~3x the fp32 path's
-    throughput) or "fp8" (Whisper only: bf16 activations, MX-fp8 QKV / fc1 / fc2 GEMMs, BASELINE
-    configs[4]), "fp16" (WavLM-base: the bf16 path with fp16 activations and operands -- the same
-    matrix-core rate, 8 more mantissa bits).
+    throughput) or "fp8" (Whisper and stable-LN WavLM, i.e. WavLM-large: bf16 activations and residual
+    stream, MX-fp8 QKV / fc1 / fc2 GEMMs, BASELINE configs[4]; post-LN WavLM (WavLM-base) is refused, it
+    misses the fp8 bar on the format alone), "fp16" (WavLM-base: the bf16 path with fp16 activations and
+    operands -- the same matrix-core rate, 8 more mantissa bits).
 
     fp16 / fp16x3 keep activations in the fp16 range: with ``check_range`` (default) every embed /
     hidden_states call synchronises and raises ``SSERangeError`` if it produced a non-finite value
@@ -131,8 +133,15 @@ class SSEModel:
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
         torch.cuda.set_device(self.device)   # make sure the HIP context exists on this device
-        _lib.check(L.sse_model_create(ctypes.byref(self._cfg), blob.ctypes.data, blob.nbytes, idx,
-                                      DTYPES[dtype], ctypes.byref(h)), "sse_model_create")
+        rc = L.sse_model_create(ctypes.byref(self._cfg), blob.ctypes.data, blob.nbytes, idx, DTYPES[dtype],
+                                ctypes.byref(h))
+        if (rc == _lib.SSE_ERR_UNSUPPORTED and DTYPES[dtype] == _lib.SSE_DTYPE_FP8 and isinstance(spec, WavLMSpec)
+                and not spec.stable_layer_norm):
+            raise _lib.SSEError(rc, f"sse_model_create({spec.name}, dtype={dtype!r}): post-LN WavLM is not supported "
+                                    f"in fp8 (its LayerNorms re-normalise the quantisation error into the stream at "
+                                    f"every sub-layer: emulated 0.093 rel-L2 against the fp8 bar of 0.08, DESIGN.md §3); "
+                                    f"use dtype='bf16' or 'fp16'")
+        _lib.check(rc, "sse_model_create")
         self._h = h
         self._ws = None
         self.check_range = bool(check_range) and dtype in FP16_RANGE
