@@ -72,7 +72,9 @@ enum sse_err {
   SSE_ERR_RANGE = -7         /* an fp16-range path produced a non-finite output (sse_check_range) */
 };
 
-/* Model shape.  Field meaning follows the HF configs (WavLMConfig / WhisperConfig). */
+/* Model shape.  Field meaning follows the HF configs (WavLMConfig / WhisperConfig; SSE_KIND_WAVLM with
+ * num_buckets == 0 is a Wav2Vec2Config / HubertConfig encoder).  hidden / heads must be 64: hubert-xlarge and
+ * XLS-R-1B / 2B (head width 80 / 120) are not built. */
 typedef struct sse_cfg {
   int32_t kind;              /* sse_kind                                              */
   int32_t hidden;            /* hidden_size / d_model                                 */
@@ -89,8 +91,11 @@ typedef struct sse_cfg {
   int32_t stable_layer_norm; /* 0: post-LN encoder (base); 1: pre-LN + final LN (large) */
   int32_t pos_kernel;        /* 128                                                   */
   int32_t pos_groups;        /* 16                                                    */
-  int32_t num_buckets;       /* 320                                                   */
-  int32_t max_distance;      /* 800                                                   */
+  int32_t num_buckets;       /* 320 (WavLM).  0: the bias-free encoder -- wav2vec 2.0 / */
+                             /* HuBERT: the blob has no rel_attn_embed / gru_rel_pos_* */
+                             /* tensors, the QKV GEMM no gate columns, the attention  */
+                             /* no bias table.  < 0 is invalid                        */
+  int32_t max_distance;      /* 800; ignored when num_buckets == 0                    */
   int32_t do_normalize;      /* Wav2Vec2FeatureExtractor.do_normalize                 */
   /* Whisper */
   int32_t n_mels;            /* 80                                                    */

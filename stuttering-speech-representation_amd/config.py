@@ -9,6 +9,8 @@ REF/whisper_embeddings_large.py:437-438) and reads the shapes from the hub
   (HF/models/wavlm/configuration_wavlm.py:159-213).
 * ``WAVLM_LARGE`` == microsoft/wavlm-large (layer-norm conv frontend, stable-LN
   encoder; HF/models/wavlm/modeling_wavlm.py:696-720, 339-373, 450-522).
+* ``WAV2VEC2_BASE`` / ``HUBERT_BASE`` / ``WAV2VEC2_LARGE_LV60`` / ``HUBERT_LARGE``: the same encoder without the gated
+  relative-position bias (``num_buckets=0``; HF/models/wav2vec2/modeling_wav2vec2.py, HF/models/hubert/modeling_hubert.py).
 * ``WHISPER_LARGE_V2`` / ``WHISPER_TINY`` == the encoder of openai/whisper-large-v2 / -tiny
   (HF/models/whisper/modeling_whisper.py:540-646).
 
@@ -39,7 +41,7 @@ class WavLMSpec:
     stable_layer_norm: bool = False    # False: post-LN encoder (base); True: pre-LN + final LN (large)
     pos_kernel: int = 128
     pos_groups: int = 16
-    num_buckets: int = 320
+    num_buckets: int = 320             # 0: no relative-position bias (wav2vec 2.0 / HuBERT); max_distance is then ignored
     max_distance: int = 800
     ln_eps: float = 1e-5
     name: str = "wavlm-base"
@@ -48,6 +50,12 @@ class WavLMSpec:
     @property
     def head_dim(self) -> int:
         return self.hidden // self.heads
+
+    @property
+    def rel_pos_bias(self) -> bool:
+        """WavLM's gated relative-position bias.  False (``num_buckets == 0``): the bias-free encoder of
+        wav2vec 2.0 / HuBERT -- the same network without ``rel_attn_embed`` and the ``gru_rel_pos_*`` gate."""
+        return self.num_buckets > 0
 
     @property
     def num_hidden_states(self) -> int:
@@ -71,6 +79,16 @@ class WavLMSpec:
 WAVLM_BASE = WavLMSpec()
 WAVLM_LARGE = WavLMSpec(hidden=1024, layers=24, heads=16, ffn=4096, feat_norm_layer=True,
                         stable_layer_norm=True, name="wavlm-large")
+# wav2vec 2.0 / HuBERT: the WavLM encoder without the gated relative-position bias (num_buckets=0; HF
+# modeling_wav2vec2.py / modeling_hubert.py share the conv frontend, positional conv and layer layout).
+# base: "group" frontend, post-LN; large-lv60 / hubert-large: "layer" frontend with conv biases, stable-LN.
+# Head width 64 only: hubert-xlarge (1280 / 16) and XLS-R-1B / 2B (1280 / 16, 1920 / 16) are not built.
+WAV2VEC2_BASE = WavLMSpec(num_buckets=0, name="wav2vec2-base")
+HUBERT_BASE = WavLMSpec(num_buckets=0, name="hubert-base")
+WAV2VEC2_LARGE_LV60 = WavLMSpec(hidden=1024, layers=24, heads=16, ffn=4096, conv_bias=True, feat_norm_layer=True,
+                                stable_layer_norm=True, num_buckets=0, name="wav2vec2-large-lv60")
+HUBERT_LARGE = WavLMSpec(hidden=1024, layers=24, heads=16, ffn=4096, conv_bias=True, feat_norm_layer=True,
+                         stable_layer_norm=True, num_buckets=0, name="hubert-large")
 
 
 @dataclass(frozen=True)
@@ -183,17 +201,19 @@ def param_specs(spec) -> list[tuple[str, tuple]]:
                  (H, H // spec.pos_groups, spec.pos_kernel)),
                 ("encoder.pos_conv_embed.conv.bias", (H,)),
                 ("encoder.layer_norm.weight", (H,)),
-                ("encoder.layer_norm.bias", (H,)),
-                ("encoder.layers.0.attention.rel_attn_embed.weight", (spec.num_buckets, spec.heads))]
+                ("encoder.layer_norm.bias", (H,))]
+        if spec.rel_pos_bias:
+            out.append(("encoder.layers.0.attention.rel_attn_embed.weight", (spec.num_buckets, spec.heads)))
         for l in range(spec.layers):
             p = f"encoder.layers.{l}"
             for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
                 out.append((f"{p}.attention.{n}.weight", (H, H)))
                 out.append((f"{p}.attention.{n}.bias", (H,)))
-            out += [(f"{p}.attention.gru_rel_pos_const", (1, spec.heads, 1, 1)),
-                    (f"{p}.attention.gru_rel_pos_linear.weight", (8, spec.head_dim)),
-                    (f"{p}.attention.gru_rel_pos_linear.bias", (8,)),
-                    (f"{p}.layer_norm.weight", (H,)),
+            if spec.rel_pos_bias:
+                out += [(f"{p}.attention.gru_rel_pos_const", (1, spec.heads, 1, 1)),
+                        (f"{p}.attention.gru_rel_pos_linear.weight", (8, spec.head_dim)),
+                        (f"{p}.attention.gru_rel_pos_linear.bias", (8,))]
+            out += [(f"{p}.layer_norm.weight", (H,)),
                     (f"{p}.layer_norm.bias", (H,)),
                     (f"{p}.feed_forward.intermediate_dense.weight", (F, H)),
                     (f"{p}.feed_forward.intermediate_dense.bias", (F,)),

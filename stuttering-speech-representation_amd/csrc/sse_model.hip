@@ -296,6 +296,8 @@ struct sse_model {
   bool pre_fold = false;  // bf16 stable-LN WavLM (large): each layer's attention LayerNorm folded into its QKV (l > 0)
   int ldq = 0;   // QKV GEMM width: 3H (+ 8*heads gate columns for WavLM, then zero pad to 256 so the
                 // 256x256 MFMA tile applies)
+  bool rel_pos = false;   // WavLM gated relative-position bias (cfg.num_buckets > 0); false: the bias-free encoder
+                          // (wav2vec 2.0 / HuBERT): no gate columns, no bias table, relb / g_const unset
   std::vector<LayerW> layers;
   // live per-launch timing (sse_profile_*): events pre-created outside any capture
   struct Prof {
@@ -339,7 +341,8 @@ bool cfg_valid(const sse_cfg* c) {
   if (c->hidden % c->heads || c->hidden / c->heads != 64) return false;
   if (c->kind == SSE_KIND_WAVLM) {
     if (c->n_conv < 2 || c->n_conv > 8 || c->pos_groups <= 0 || c->hidden % c->pos_groups) return false;
-    if (c->max_distance > MAXD) return false;   // the clamp to +-MAXD must lie in the saturated range
+    if (c->num_buckets < 0) return false;       // 0: the bias-free encoder (wav2vec 2.0 / HuBERT)
+    if (c->num_buckets > 0 && c->max_distance > MAXD) return false;   // the clamp to +-MAXD must lie in the saturated range
   } else if (c->kind == SSE_KIND_WHISPER) {
     if (c->n_mels <= 0 || c->max_positions <= 0) return false;
     if (c->decoder_layers < 0 || (c->decoder_layers > 0 && c->dec_ffn <= 0)) return false;
@@ -349,11 +352,20 @@ bool cfg_valid(const sse_cfg* c) {
   return true;
 }
 
+// Gate columns of the WavLM QKV GEMM (8 per head, gru_rel_pos_linear); none for the bias-free encoder
+int wavlm_gate_cols(const sse_cfg& c) { return c.num_buckets > 0 ? 8 * c.heads : 0; }
+// QKV GEMM width of a WavLM-kind model: q | k | v | gate columns | zero pad to the 256-column tile
+int wavlm_ldq(const sse_cfg& c) { return ((3 * c.hidden + wavlm_gate_cols(c) + 255) / 256) * 256; }
+
 // Walk the canonical order; with a null blob only counts.
 int build_wavlm(sse_model* m, Blob& bl, Arena& ar) {
   const sse_cfg& c = m->cfg;
   const int BF = m->ekind();   // weight element kind (fp32 / bf16 / fp16)
   const int H = c.hidden, F = c.ffn, nh = c.heads;
+  // num_buckets == 0: a wav2vec 2.0 / HuBERT encoder -- the blob has no rel_attn_embed and no gru_rel_pos_*
+  // tensors, the QKV rows are q | k | v | zero pad, and the attention runs its bias-free instantiations
+  const bool relpos = c.num_buckets > 0;
+  m->rel_pos = relpos;
   int cin = 1;
   for (int i = 0; i < c.n_conv; ++i) {
     const int co = c.conv_dim[i], k = c.conv_kernel[i];
@@ -390,7 +402,7 @@ int build_wavlm(sse_model* m, Blob& bl, Arena& ar) {
   const float* pb = bl.take(H);
   const float* elw = bl.take(H);
   const float* elb = bl.take(H);
-  const float* rel = bl.take((size_t)c.num_buckets * nh);
+  const float* rel = relpos ? bl.take((size_t)c.num_buckets * nh) : nullptr;
   if (!bl.ok) return SSE_ERR_WEIGHTS;
   if (fplw) {
     m->fp_ln_w = ar.put_f32(fplw, C);
@@ -414,12 +426,14 @@ int build_wavlm(sse_model* m, Blob& bl, Arena& ar) {
     m->pos_b = ar.put_f32(pb, H);
     m->enc_ln_w = ar.put_f32(elw, H);
     m->enc_ln_b = ar.put_f32(elb, H);
-    std::vector<float> tab((size_t)nh * (2 * MAXD + 1));
-    for (int d = -MAXD; d <= MAXD; ++d) {
-      const int bk = rel_bucket(d, c.num_buckets, c.max_distance);
-      for (int h = 0; h < nh; ++h) tab[(size_t)h * (2 * MAXD + 1) + d + MAXD] = rel[(size_t)bk * nh + h];
+    if (relpos) {
+      std::vector<float> tab((size_t)nh * (2 * MAXD + 1));
+      for (int d = -MAXD; d <= MAXD; ++d) {
+        const int bk = rel_bucket(d, c.num_buckets, c.max_distance);
+        for (int h = 0; h < nh; ++h) tab[(size_t)h * (2 * MAXD + 1) + d + MAXD] = rel[(size_t)bk * nh + h];
+      }
+      m->relb = ar.put_f32(tab.data(), tab.size());
     }
-    m->relb = ar.put_f32(tab.data(), tab.size());
   }
   const bool fold = m->half() && !c.stable_layer_norm && H == 768;   // the GEMM epilogues combine 3 column-tile partials
   // stable-LN (pre-LN, WavLM-large) in bf16: the QKV of layers l > 0 reads the bf16 residual stream itself with
@@ -431,7 +445,8 @@ int build_wavlm(sse_model* m, Blob& bl, Arena& ar) {
   for (int l = 0; l < c.layers; ++l) {
     const float *qw = bl.take((size_t)H * H), *qb = bl.take(H), *kw = bl.take((size_t)H * H), *kb = bl.take(H);
     const float *vw = bl.take((size_t)H * H), *vb = bl.take(H), *ow = bl.take((size_t)H * H), *ob = bl.take(H);
-    const float *gc = bl.take(nh), *gw = bl.take((size_t)8 * 64), *gbb = bl.take(8);
+    const float *gc = relpos ? bl.take(nh) : nullptr, *gw = relpos ? bl.take((size_t)8 * 64) : nullptr;
+    const float* gbb = relpos ? bl.take(8) : nullptr;
     const float *l1w = bl.take(H), *l1b = bl.take(H);
     const float *f1w = bl.take((size_t)F * H), *f1b = bl.take(F), *f2w = bl.take((size_t)H * F), *f2b = bl.take(H);
     const float *l2w = bl.take(H), *l2b = bl.take(H);
@@ -439,8 +454,9 @@ int build_wavlm(sse_model* m, Blob& bl, Arena& ar) {
     if (!qw) continue;
     LayerW L{};
     // rows [q | k | v | gate: head h, output o at 3H + 8h + o, block-diagonal over the
-    // head's 64 input channels (gru_rel_pos_linear, HF :158-163) | zero pad to ldq]
-    const int ldq = ((3 * H + 8 * nh + 255) / 256) * 256;
+    // head's 64 input channels (gru_rel_pos_linear, HF :158-163) | zero pad to ldq]; the bias-free encoder has
+    // no gate rows: q | k | v | zero pad
+    const int ldq = wavlm_ldq(c);
     m->ldq = ldq;
     std::vector<float> qkv((size_t)ldq * H, 0.f), qkvb((size_t)ldq, 0.f);
     std::memcpy(qkv.data(), qw, (size_t)H * H * 4);
@@ -449,7 +465,7 @@ int build_wavlm(sse_model* m, Blob& bl, Arena& ar) {
     std::memcpy(qkvb.data(), qb, H * 4);
     std::memcpy(qkvb.data() + H, kb, H * 4);
     std::memcpy(qkvb.data() + 2 * H, vb, H * 4);
-    for (int hh = 0; hh < nh; ++hh)
+    for (int hh = 0; relpos && hh < nh; ++hh)
       for (int o = 0; o < 8; ++o) {
         const size_t row = (size_t)3 * H + 8 * hh + o;
         for (int d = 0; d < 64; ++d) qkv[row * H + hh * 64 + d] = gw[o * 64 + d];
@@ -465,9 +481,11 @@ int build_wavlm(sse_model* m, Blob& bl, Arena& ar) {
     L.o_w = X3 ? ar.put_x3(std::vector<float>(ow, ow + (size_t)H * H), H, 1, H)
                : ar.put_elem(std::vector<float>(ow, ow + (size_t)H * H), BF);
     L.o_b = ar.put_f32(ob, H);
-    L.g_const = ar.put_f32(gc, nh);
-    L.g_w = ar.put_f32(gw, 8 * 64);
-    L.g_b = ar.put_f32(gbb, 8);
+    if (relpos) {
+      L.g_const = ar.put_f32(gc, nh);
+      L.g_w = ar.put_f32(gw, 8 * 64);
+      L.g_b = ar.put_f32(gbb, 8);
+    }
     L.ln1_w = ar.put_f32(l1w, H);
     L.ln1_b = ar.put_f32(l1b, H);
     if (MX) L.f1_q = ar.put_mx(std::vector<float>(f1w, f1w + (size_t)F * H), F, H, &L.f1_s);
@@ -748,7 +766,7 @@ WavlmWs wavlm_plan(const sse_model* m, int B, int L, Plan& p) {
     return plain > mxb ? plain : mxb;
   };
   w.xb = p.add(opnd(M * (H > c.conv_dim[c.n_conv - 1] ? H : c.conv_dim[c.n_conv - 1]) * es, H));
-  w.qkv = p.add(M * (size_t)(((3 * H + 8 * c.heads + 255) / 256) * 256) * es);
+  w.qkv = p.add(M * (size_t)wavlm_ldq(c) * es);
   w.ctx = p.add(M * H * es);
   w.ff = p.add(opnd(M * (size_t)c.ffn * es, c.ffn));
   w.hf = c.stable_layer_norm ? p.add(M * H * 4) : 0;
@@ -913,6 +931,7 @@ int wavlm_forward(sse_model* m, const float* wave, int B, int L, const Sink& sin
   int Ts[8];
   const int Tf = wavlm_frames(c, L, Ts);
   const int H = c.hidden, nh = c.heads, F = c.ffn;
+  const double ng = wavlm_gate_cols(c);   // gate columns of the QKV GEMM (FLOP / byte counts)
   const int M = B * Tf;
   const float eps = c.ln_eps;
   void* zero = ws + w.zero;
@@ -1045,7 +1064,7 @@ int wavlm_forward(sse_model* m, const float* wave, int B, int L, const Sink& sin
         RC(launch_layernorm_mx<bf16>(x16, m->ptr<float>(Lw.ln1_w), m->ptr<float>(Lw.ln1_b), M, H, eps, xq, xq_s, s));
         // all ldq columns (q | k | v | gate | pad) in one GEMM, bf16 out; FLOPs of the useful columns, as gemm:qkv
         RC(mx_gemm<bf16>(m, s, "gemm_mx:qkv", M, xq, xq_s, Lw.qkv_q, Lw.qkv_s, Lw.qkv_b, m->ldq, H, nullptr, qkv, nullptr,
-                         ACT_NONE, zero, 2.0 * M * (3.0 * H + 8.0 * nh) * H));
+                         ACT_NONE, zero, 2.0 * M * (3.0 * H + ng) * H));
       }
     } else {
       if (pre16) {
@@ -1066,13 +1085,15 @@ int wavlm_forward(sse_model* m, const float* wave, int B, int L, const Sink& sin
         g.apart = p2; g.apart_nt = nt; g.ln_eps = eps;
       }
       // algorithmic FLOPs count the 3H + 8*heads useful columns, not the zero pad to ldq
-      RC(prof(m, s, "gemm:qkv", 2.0 * M * (3.0 * H + 8.0 * nh) * H, gbytes<T>(g),
+      RC(prof(m, s, "gemm:qkv", 2.0 * M * (3.0 * H + ng) * H, gbytes<T>(g),
               [&] { return launch_gemm<T>(g, AMODE_SEG, 1, s); }));
     }
     AttnArgs a{};
     a.qkv = qkv; a.out = ctx; a.T = Tf; a.H = H; a.nh = nh; a.ldq = m->ldq; a.scale = 0.125f;
-    a.gconst = m->ptr<float>(Lw.g_const); a.relb = m->ptr<float>(m->relb); a.maxd = MAXD; a.tlen = tflen;
-    RC(prof(m, s, "attn", 4.0 * B * (double)Tf * Tf * H, (double)B * Tf * (4.0 * H + 8.0 * nh) * sizeof(T),
+    // the bias-free encoder (wav2vec 2.0 / HuBERT): no gate, no table -> launch_attention's relb == nullptr branches
+    a.gconst = m->rel_pos ? m->ptr<float>(Lw.g_const) : nullptr;
+    a.relb = m->rel_pos ? m->ptr<float>(m->relb) : nullptr; a.maxd = MAXD; a.tlen = tflen;
+    RC(prof(m, s, "attn", 4.0 * B * (double)Tf * Tf * H, (double)B * Tf * (4.0 * H + ng) * sizeof(T),
             [&] { return launch_attention<T>(a, B, s); }));
     g = GemmArgs{};
     g.A = ctx; g.B = m->ptr(Lw.o_w); g.M = M; g.N = H; g.K = H; g.rows_per_seg = M; g.lda = H;
@@ -1193,7 +1214,7 @@ X3Ws x3_plan(const sse_model* m, int B, int L, Plan& p) {
   w.x = p.add(M * H * 4);
   w.xt = p.add(M * H * 4);
   w.xb = p.add(M * (size_t)(H > Cl ? H : Cl) * 6);
-  w.qkv = p.add(M * (size_t)(((3 * H + 8 * c.heads + 255) / 256) * 256) * 4);
+  w.qkv = p.add(M * (size_t)wavlm_ldq(c) * 4);
   w.ctx3 = p.add(M * H * 6);
   w.ff = p.add(M * (size_t)c.ffn * 6);
   w.fr = p.add((size_t)B * 8);
@@ -1213,6 +1234,7 @@ int wavlm_forward_x3(sse_model* m, const float* wave, int B, int L, const Sink& 
   int Ts[8];
   const int Tf = wavlm_frames(c, L, Ts);
   const int H = c.hidden, nh = c.heads, F = c.ffn;
+  const double ng = wavlm_gate_cols(c);   // gate columns of the QKV GEMM (FLOP / byte counts)
   const int M = B * Tf;
   const float eps = c.ln_eps;
   void* zero = ws + w.zero;
@@ -1323,13 +1345,15 @@ int wavlm_forward_x3(sse_model* m, const float* wave, int B, int L, const Sink& 
     g.zero = zero;
     g.f16 = 1;
     g.alpha = m->alpha(Lw.qkv_w);
-    RC(prof(m, s, "gemm:qkv", 2.0 * M * (3.0 * H + 8.0 * nh) * H, gbytes<bf16>(g),
+    RC(prof(m, s, "gemm:qkv", 2.0 * M * (3.0 * H + ng) * H, gbytes<bf16>(g),
             [&] { return launch_gemm8_bf16(g, s); }));
     AttnArgs a{};
     a.qkv = qkv; a.out = ctx3; a.out3 = 1; a.T = Tf; a.H = H; a.nh = nh; a.ldq = m->ldq; a.scale = 0.125f;
-    a.gconst = m->ptr<float>(Lw.g_const); a.relb = m->ptr<float>(m->relb); a.maxd = MAXD; a.tlen = tflen;
+    // the bias-free encoder (wav2vec 2.0 / HuBERT): no gate, no table -> launch_attention's relb == nullptr branches
+    a.gconst = m->rel_pos ? m->ptr<float>(Lw.g_const) : nullptr;
+    a.relb = m->rel_pos ? m->ptr<float>(m->relb) : nullptr; a.maxd = MAXD; a.tlen = tflen;
     // the attention writes the out-projection's tripled operand itself (no fp32 context round trip)
-    RC(prof(m, s, "attn", 4.0 * B * (double)Tf * Tf * H, (double)B * Tf * ((3.0 * H + 8.0 * nh) * 4.0 + 6.0 * H),
+    RC(prof(m, s, "attn", 4.0 * B * (double)Tf * Tf * H, (double)B * Tf * ((3.0 * H + ng) * 4.0 + 6.0 * H),
             [&] { return launch_attention<float>(a, B, s); }));
     g = GemmArgs{};
     g.A = ctx3; g.B = m->ptr(Lw.o_w); g.M = M; g.N = H; g.K = 3 * H; g.rows_per_seg = M; g.lda = 3 * H;

@@ -10,8 +10,8 @@ Return ``{"layer_<i>": float32[H]}`` (or ``encoder_layer_<i>``); ``None`` plus a
 any error, never raise; OOM is recognised by exception type (``torch.OutOfMemoryError`` /
 ``SSEOutOfMemoryError``), not by the "CUDA out of memory" string the reference matches.
 
-When ``model`` is one of this package's objects (hf.WavLMModel / hf.WhisperModel) the
-hidden states are never materialised: the fused ``sse_embed`` path pools them on the GPU.
+When ``model`` is one of this package's objects (hf.WavLMModel / hf.Wav2Vec2Model / hf.HubertModel /
+hf.WhisperModel) the hidden states are never materialised: the fused ``sse_embed`` path pools them on the GPU.
 Any other HF-compatible model object takes the reference's generic route.
 """
 from __future__ import annotations
@@ -24,7 +24,7 @@ import torch
 
 from . import config as C
 from ._lib import SSEOutOfMemoryError
-from .hf import WavLMModel, WhisperModel
+from .hf import WaveEncoderModel, WhisperModel
 from .model import POOL_STATS, pool_mask
 
 logger = logging.getLogger(__name__)
@@ -137,7 +137,7 @@ def extract_embeddings_from_audio_wavlm(audio_array, model, feature_extractor, d
     try:
         inputs = feature_extractor(audio_array, sampling_rate=16000, return_tensors="pt").to(device)
         with torch.no_grad():
-            if isinstance(model, WavLMModel):
+            if isinstance(model, WaveEncoderModel):   # the WavLM / wav2vec 2.0 / HuBERT twins
                 n_hs = model.sse.spec.layers + 1
                 valid = [i for i in layer_indices if i < n_hs]
                 for i in layer_indices:

@@ -136,6 +136,52 @@ def wavlm_spec_from_config(c) -> C.WavLMSpec:
     return _canonical(spec, (C.WAVLM_BASE, C.WAVLM_LARGE))
 
 
+def _bias_free_spec(c, family: str, known) -> C.WavLMSpec:
+    """The shared body of wav2vec2_spec_from_config / hubert_spec_from_config: a wav2vec 2.0 / HuBERT encoder is
+    the WavLM encoder without the gated relative-position bias (``num_buckets=0``).  Every config field that would
+    change the network this path builds is refused by name, on the host."""
+    if getattr(c, "add_adapter", False):
+        raise NotImplementedError("add_adapter=True: the adapter layers after the encoder are not built")
+    if getattr(c, "conv_pos_batch_norm", False):
+        raise NotImplementedError("conv_pos_batch_norm=True: the batch-norm positional conv is not built "
+                                  "(only the weight-normed one)")
+    if not getattr(c, "feat_proj_layer_norm", True):
+        raise NotImplementedError("feat_proj_layer_norm=False: the feature projection is built with its LayerNorm")
+    if c.feat_extract_activation != "gelu":
+        raise NotImplementedError(f"feat_extract_activation={c.feat_extract_activation!r}: only 'gelu' is built")
+    if c.hidden_act != "gelu":
+        raise NotImplementedError(f"hidden_act={c.hidden_act!r}: only 'gelu' is built")
+    if c.feat_extract_norm not in ("group", "layer"):
+        raise NotImplementedError(f"feat_extract_norm={c.feat_extract_norm!r}")
+    if c.hidden_size % c.num_attention_heads or c.hidden_size // c.num_attention_heads != 64:
+        raise NotImplementedError(
+            f"hidden_size / num_attention_heads = {c.hidden_size} / {c.num_attention_heads}: only a head width of 64 "
+            f"is built (base and large shapes); hubert-xlarge and XLS-R-1B / 2B (head width 80 / 120) are out of scope")
+    spec = C.WavLMSpec(hidden=c.hidden_size, layers=c.num_hidden_layers, heads=c.num_attention_heads,
+                       ffn=c.intermediate_size, conv_dim=tuple(c.conv_dim), conv_kernel=tuple(c.conv_kernel),
+                       conv_stride=tuple(c.conv_stride), conv_bias=bool(c.conv_bias),
+                       feat_norm_layer=c.feat_extract_norm == "layer",
+                       stable_layer_norm=bool(c.do_stable_layer_norm), pos_kernel=c.num_conv_pos_embeddings,
+                       pos_groups=c.num_conv_pos_embedding_groups, num_buckets=0, ln_eps=c.layer_norm_eps,
+                       name=getattr(c, "_name_or_path", "") or family)
+    return _canonical(spec, known)
+
+
+def wav2vec2_spec_from_config(c) -> C.WavLMSpec:
+    """transformers ``Wav2Vec2Config`` -> a bias-free ``WavLMSpec`` (host only, no GPU).  ``Wav2Vec2Config()`` maps
+    to ``C.WAV2VEC2_BASE``, the wav2vec2-large-lv60 shape to ``C.WAV2VEC2_LARGE_LV60``.  Raises
+    NotImplementedError naming the field for adapters, the batch-norm positional conv, a feature projection
+    without LayerNorm, non-GELU activations, an unknown ``feat_extract_norm`` and head widths other than 64."""
+    return _bias_free_spec(c, "wav2vec2", (C.WAV2VEC2_BASE, C.WAV2VEC2_LARGE_LV60))
+
+
+def hubert_spec_from_config(c) -> C.WavLMSpec:
+    """transformers ``HubertConfig`` -> a bias-free ``WavLMSpec`` (host only): ``HubertConfig()`` maps to
+    ``C.HUBERT_BASE``, the hubert-large shape to ``C.HUBERT_LARGE``; refusals as wav2vec2_spec_from_config
+    (hubert-xlarge, head width 80, is one of them)."""
+    return _bias_free_spec(c, "hubert", (C.HUBERT_BASE, C.HUBERT_LARGE))
+
+
 def whisper_spec_from_config(c, with_decoder: bool = True) -> C.WhisperSpec:
     """transformers ``WhisperConfig`` -> ``WhisperSpec`` (host only, no GPU), read by
     ``WhisperModel.from_hf`` (REF/whisper_embeddings_large.py:437-438 loads the HF model this maps).
@@ -184,9 +230,13 @@ class _DuckModel:
                               valid_only=valid_only, frames=frames)
 
 
-class WavLMModel(_DuckModel):
-    """WavLMModel twin.  ``WavLMModel.from_hf(hf_model)`` takes the weights of a real
-    transformers WavLMModel (e.g. a hub checkpoint loaded elsewhere)."""
+class WaveEncoderModel(_DuckModel):
+    """The shared twin of the raw-waveform encoders (WavLM, wav2vec 2.0, HuBERT): one conv frontend + transformer
+    encoder on the HIP path; the subclasses differ in how an HF config maps to the spec.  Keys of the state dict
+    that the spec does not name (``masked_spec_embed``, the quantizer / projection heads of a ``ForPreTraining``
+    checkpoint) are ignored."""
+
+    _spec_from_config = staticmethod(wavlm_spec_from_config)
 
     @classmethod
     def from_state_dict(cls, spec, state_dict, device="cuda:0", dtype="fp32"):
@@ -194,7 +244,7 @@ class WavLMModel(_DuckModel):
 
     @classmethod
     def from_hf(cls, hf_model, device="cuda:0", dtype="fp32"):
-        return cls.from_state_dict(wavlm_spec_from_config(hf_model.config), hf_model.state_dict(), device, dtype)
+        return cls.from_state_dict(cls._spec_from_config(hf_model.config), hf_model.state_dict(), device, dtype)
 
     def __call__(self, input_values, attention_mask=None, output_hidden_states=None, return_dict=True, **_):
         if attention_mask is not None:
@@ -203,6 +253,24 @@ class WavLMModel(_DuckModel):
         return BaseModelOutput(last_hidden_state=hs[-1], hidden_states=hs if output_hidden_states else None)
 
     forward = __call__
+
+
+class WavLMModel(WaveEncoderModel):
+    """WavLMModel twin.  ``WavLMModel.from_hf(hf_model)`` takes the weights of a real
+    transformers WavLMModel (e.g. a hub checkpoint loaded elsewhere)."""
+
+
+class Wav2Vec2Model(WaveEncoderModel):
+    """Wav2Vec2Model twin (the bias-free attention path, ``num_buckets=0``): ``Wav2Vec2Model.from_hf(hf_model)``
+    takes a transformers Wav2Vec2Model of the base or large-lv60 shape."""
+
+    _spec_from_config = staticmethod(wav2vec2_spec_from_config)
+
+
+class HubertModel(WaveEncoderModel):
+    """HubertModel twin (the bias-free attention path): base and large shapes."""
+
+    _spec_from_config = staticmethod(hubert_spec_from_config)
 
 
 class _WhisperEncoder:

@@ -109,6 +109,10 @@ class SSEModel:
     misses the fp8 bar on the format alone), "fp16" (WavLM-base: the bf16 path with fp16 activations and
     operands -- the same matrix-core rate, 8 more mantissa bits).
 
+    A ``WavLMSpec`` with ``num_buckets=0`` (config.WAV2VEC2_* / HUBERT_*) is a wav2vec 2.0 / HuBERT encoder: the
+    same network without the gated relative-position bias (no gate columns in the QKV GEMM, the bias-free
+    attention kernels); every dtype rule above holds for it by shape (fp8: the stable-LN large shapes only).
+
     fp16 / fp16x3 keep activations in the fp16 range: with ``check_range`` (default) every embed /
     hidden_states call synchronises and raises ``SSERangeError`` if it produced a non-finite value
     (an overflow); throughput loops pass ``check_range=False`` and call ``check_range_now()`` once."""
@@ -118,6 +122,10 @@ class SSEModel:
         if not isinstance(spec, (WavLMSpec, WhisperSpec)):
             raise TypeError(spec)
         self.spec = spec
+        if spec.hidden % spec.heads or spec.head_dim != 64:
+            raise ValueError(f"{spec.name}: hidden / heads = {spec.hidden} / {spec.heads}: the attention kernels are "
+                             f"built for a head width of 64 (hubert-xlarge and XLS-R-1B / 2B, head width 80 / 120, "
+                             f"are out of scope)")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("SSEModel runs on a GPU device (no CPU fallback)")
